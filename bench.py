@@ -7,7 +7,13 @@ tracks x 100 steps, fp64, shared F/H/Q/R, one fk_kf_batch_filter_f64 launch per 
 KalmanFilter.batch_filter written: means, covariances, means_p, covariances_p).
 Inputs (z, x0, P0) are resident in HBM before the timed region.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --dump-outputs DIR then also writes
+what the last timed step computed for a fixed, seeded sample of tracks (DIR/<name>.npy, float64, < 64 MB), so two
+builds can be compared output for output.  --full adds everything else the line has carried: the parity check
+against the oracle, the other placements' launch times, the roofline, GPU clocks, HBM probes, the CPU baseline and
+the rows of BASELINE configs[2..4].
 
 N > 1: one rank per GPU under torch.distributed.run -- either the caller launches it that way
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment) or, when `python bench.py --gpus N`
@@ -16,7 +22,7 @@ with an error if the node has fewer than N GPUs).  Tracks shard across ranks (we
 rank filters its own 1e6 tracks, no data-path collective), then one RCCL all-gather of the summary
 state (final x of every track) per step.
 
-Prints ONE JSON line (rank 0) with `roofline` (HBM) and, at N=1, `cpu_baseline`
+Prints ONE JSON line (rank 0); with --full it also holds `roofline` (HBM) and, at N=1, `cpu_baseline`
 (the NumPy oracle = the reference's algorithm, timed on this host's cores).
 """
 import argparse
@@ -257,6 +263,28 @@ def parity_rel_err(got, ref):
     return float("nan") if not np.all(np.isfinite(g2)) else float(np.max(d))
 
 
+DUMP_TRACKS = 1536                     # x 100 steps x 40 doubles (x, P, x_p, P_p) = 49 MB: under the 64 MB of --dump-outputs
+
+
+def dump_sample(N, k=DUMP_TRACKS):
+    """The tracks --dump-outputs writes: the first k/3 and a seeded random 2k/3 of the rest (all of them when N <= k).
+    Fixed for a given N, so two runs with the same arguments write the same records."""
+    if N <= k:
+        return np.arange(N)
+    head = k // 3
+    rs = np.random.RandomState(20240613)
+    return np.concatenate([np.arange(head), head + np.sort(rs.choice(N - head, size=k - head, replace=False))])
+
+
+def dump_outputs(path, sample, got):
+    """--dump-outputs: the four batch_filter outputs of the sampled tracks, (T, K, n) / (T, K, n, n) float64 in NumPy order
+    whatever the layout, and the sampled track indices."""
+    os.makedirs(path, exist_ok=True)
+    arrays = dict(zip(("means", "covs", "means_p", "covs_p"), got), tracks=sample)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def gpu_clocks():
     """sclk / mclk / power of GPU 0 from rocm-smi (recorded next to the measurement: boxes of the pool differ)."""
     import subprocess
@@ -436,13 +464,20 @@ def main():
                     help="weak (default; the driver's scaling run): every rank filters --tracks tracks of its own.  strong: "
                          "BASELINE configs[1] read literally -- --tracks tracks IN TOTAL, rank r the contiguous shard "
                          "parallel.shard_bounds(tracks, r, N) (125000 per GPU at N = 8: launch and tail cost show)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the parity check against the oracle, the launch time of every placement, the "
+                         "roofline, GPU clocks and HBM probes, the CPU baseline and the rows of BASELINE configs[2..4] (all after "
+                         "the timed region).  Off: the run does only what the headline needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the four outputs of the last step for a fixed, seeded sample of tracks "
+                         "(rank 0's) as DIR/<name>.npy, float64, under 64 MB in all")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the rows of BASELINE configs[2..4] (the line's \"configs\" key; after the timed region, rank 0 at N = 1 only)")
+                    help="with --full: skip the rows of BASELINE configs[2..4] (the line's \"configs\" key; after the timed region, rank 0 at N = 1 only)")
     ap.add_argument("--config-reps", type=int, default=10, help="event-timed launches per row of \"configs\"")
     ap.add_argument("--T", type=int, default=100)
     ap.add_argument("--layout", default=os.environ.get("FK_BENCH_LAYOUT", "aos"), choices=["soa", "aos"],
                     help="record layout of z and the outputs: aos = NumPy C order [T][N][n][n] (default), soa = [T][n*n][N]")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--placement", default=os.environ.get("FK_BENCH_PLACEMENT", "auto"), choices=["auto", "interleave", "probe", "none"],
                     help="how the two covariance histories (76 %% of the bytes) are allocated -- every mode is a mode of the product "
                          "API KalmanFilterBank.batch_filter(device_outputs=True, ...).  auto (default) = the API called without "
@@ -552,14 +587,16 @@ def main():
                                  "auto": "the API's default at this size: two arrays placed by measurement "
                                          "(filterpy_amd.placement.placed_pair; KalmanFilterBank.batch_filter(device_outputs=True))"}[args.placement]}
     med3 = lambda *b: (one_launch_ms(*b), float(np.median([one_launch_ms(*b) for _ in range(3)])))[1]  # noqa: E731
-    placement_info["two_arrays_ms"] = round(med3(covs, covs_p), 4)
+    if args.full:                                          # (a plain run allocates the same arrays in the same order, untimed)
+        placement_info["two_arrays_ms"] = round(med3(covs, covs_p), 4)
     shape, csize = tuple(covs.shape), covs.numel() * 8
     if args.placement != "none":
         del covs, covs_p
         torch.cuda.empty_cache()
         cov2, c_il, cp_il = E.alloc_cov_pair(T, N, n, layout, device)
         desc["flags"] = _abi.FK_KF_FLAG_COV_INTERLEAVED
-        placement_info["interleave_ms"] = round(med3(c_il, cp_il), 4)
+        if args.full:
+            placement_info["interleave_ms"] = round(med3(c_il, cp_il), 4)
         if args.placement == "interleave":
             covs, covs_p = c_il, cp_il
         else:
@@ -631,35 +668,45 @@ def main():
     elapsed = time.perf_counter() - t0
     elapsed = parallel.max_over_ranks(elapsed, device)
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in events])) if events else float("nan")
-    assert int(status.abs().max()) == 0, "kernel flagged tracks"
 
-    # parity on the timed buffers (not timed): the first K tracks + K random tracks, all T steps, all four
-    # outputs, against the oracle (K = 1024); normwise per vector / matrix, NaN fails
-    K = max(1, min(args.parity_tracks, N // 2))
-    rs = np.random.RandomState(99 + rank)
-    sample = np.concatenate([np.arange(K), K + np.sort(rs.choice(N - K, size=K, replace=False))])
-    idx = torch.as_tensor(sample, device=device)
-    if layout == "aos":
-        zs_h = z[:, idx].cpu().numpy()
-        got = [means[:, idx].cpu().numpy(), covs[:, idx].cpu().numpy().reshape(T, -1, n, n),
-               means_p[:, idx].cpu().numpy(), covs_p[:, idx].cpu().numpy().reshape(T, -1, n, n)]
-    else:
-        zs_h = z[:, :, idx].cpu().numpy().transpose(0, 2, 1)
-        tr = lambda a: a[:, :, idx].cpu().numpy().transpose(0, 2, 1)
-        got = [tr(means), tr(covs).reshape(T, -1, n, n), tr(means_p), tr(covs_p).reshape(T, -1, n, n)]
-    ref = kf_oracle.kf_batch_filter_tracks(np.zeros((len(sample), n)), np.tile(100.0 * np.eye(n), (len(sample), 1, 1)),
-                                           zs_h, F, Q, H, R, tracks=range(len(sample)))
-    worst = max(parity_rel_err(g_, r_) for g_, r_ in zip(got, ref))
-    assert np.isfinite(worst) and worst < 1e-10, f"parity vs oracle failed: {worst}"
+    def download(sample):
+        """z and the four outputs of the tracks `sample` from the timed buffers, (T, K, ...) in NumPy order whatever the layout"""
+        idx = torch.as_tensor(sample, device=device)
+        if layout == "aos":
+            zs_h = z[:, idx].cpu().numpy()
+            got = [means[:, idx].cpu().numpy(), covs[:, idx].cpu().numpy().reshape(T, -1, n, n),
+                   means_p[:, idx].cpu().numpy(), covs_p[:, idx].cpu().numpy().reshape(T, -1, n, n)]
+        else:
+            zs_h = z[:, :, idx].cpu().numpy().transpose(0, 2, 1)
+            tr = lambda a: a[:, :, idx].cpu().numpy().transpose(0, 2, 1)                  # noqa: E731
+            got = [tr(means), tr(covs).reshape(T, -1, n, n), tr(means_p), tr(covs_p).reshape(T, -1, n, n)]
+        return zs_h, got
 
-    if exchange:                                           # the gathered summary state is every rank's final x, in rank order
-        last = (args.steps - 1) % 2
-        mine = ex.gathered[last][rank]
-        if ragged:
-            mine = mine[:N] if layout == "aos" else mine[:, :N]
-        assert torch.equal(mine, xbuf[last]), "all-gather returned something else than this rank's final state"
+    if args.dump_outputs and rank == 0:                    # what the last timed step computed (every step computes the same)
+        dsample = dump_sample(N)
+        dump_outputs(args.dump_outputs, dsample, download(dsample)[1])
+
+    if args.full:
+        assert int(status.abs().max()) == 0, "kernel flagged tracks"
+        # parity on the timed buffers (not timed): the first K tracks + K random tracks, all T steps, all four
+        # outputs, against the oracle (SURVEY 8d: K = 1024); normwise per vector / matrix, NaN fails
+        K = max(1, min(args.parity_tracks, N // 2))
+        rs = np.random.RandomState(99 + rank)
+        sample = np.concatenate([np.arange(K), K + np.sort(rs.choice(N - K, size=K, replace=False))])
+        zs_h, got = download(sample)
+        ref = kf_oracle.kf_batch_filter_tracks(np.zeros((len(sample), n)), np.tile(100.0 * np.eye(n), (len(sample), 1, 1)),
+                                               zs_h, F, Q, H, R, tracks=range(len(sample)))
+        worst = max(parity_rel_err(g_, r_) for g_, r_ in zip(got, ref))
+        assert np.isfinite(worst) and worst < 1e-10, f"parity vs oracle failed: {worst}"
+
+        if exchange:                                       # the gathered summary state is every rank's final x, in rank order
+            last = (args.steps - 1) % 2
+            mine = ex.gathered[last][rank]
+            if ragged:
+                mine = mine[:N] if layout == "aos" else mine[:, :N]
+            assert torch.equal(mine, xbuf[last]), "all-gather returned something else than this rank's final state"
     per_rank = None
-    if world > 1:                                          # every rank's own launch time and shard (one small collective, after the timed region)
+    if args.full and world > 1:                            # every rank's own launch time and shard (one small collective, after the timed region)
         try:
             mine = torch.tensor([kernel_ms, float(N)], dtype=torch.float64, device=device)
             allr = torch.empty((world, 2), dtype=torch.float64, device=device)
@@ -668,10 +715,7 @@ def main():
         except Exception as exc:                           # the measurement does not depend on it
             per_rank = {"error": repr(exc)[:200]}
     if rank == 0:
-        traffic, traffic_source = pmc_traffic(layout, "interleave" if desc.get("flags") else "none")
         units = float(N_total) * T * args.steps
-        alg_bytes = 8.0 * (m + 2 * n + 2 * n * n) * N * T + 2 * 8.0 * (n + n * n) * N   # per launch
-        achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
         out = {
             "metric": "track-steps/sec (predict+update) at dim_x=4 dim_z=2",
             "value": units / elapsed, "unit": "track-steps/s", "n_gpus": world, "steps": args.steps,
@@ -688,15 +732,24 @@ def main():
                                      "probe": "probe = KalmanFilterBank.batch_filter(device_outputs=True, placement='probe')",
                                      "none": "none = KalmanFilterBank.batch_filter(device_outputs=True, cov_interleave=False)"}[args.placement],
                        "parallelism": f"tracks sharded over {world} GPU(s)" + (", RCCL all-gather of final x per step" if world > 1 else "")},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "kernel": "fk::kf_fast_kernel<4,2," + layout + ",nomask,outs" + (",IL" if desc.get("flags") else "") + "> (variant " + os.environ.get("FK_FAST_VARIANT", "0") + ")", "kernel_ms": kernel_ms,
-                         "algorithmic_bytes_per_launch": alg_bytes},
-            # the same launch on two plain torch allocations (no placement): what the 55-pair probe of `placement` buys on this box
-            "value_unplaced": float(N) * T / (placement_info["two_arrays_ms"] * 1e-3) * world,
-            "parity_max_rel_vs_oracle": worst, "parity_tracks": int(len(sample)), "placement": placement_info,
-            "gpu_clocks": gpu_clocks(), "hbm_probes": hbm_probes(device), "under_load": clocks_under_load(lambda: step(0, None, False)),   # rank 0 alone: no collective in the burst
+            "placement": placement_info,
         }
+        if args.dump_outputs:
+            out["dumped"] = {"dir": args.dump_outputs, "tracks": int(len(dsample))}
+        if args.full:
+            traffic, traffic_source = pmc_traffic(layout, "interleave" if desc.get("flags") else "none")
+            alg_bytes = 8.0 * (m + 2 * n + 2 * n * n) * N * T + 2 * 8.0 * (n + n * n) * N   # per launch
+            achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
+            out.update({
+                "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                             "kernel": "fk::kf_fast_kernel<4,2," + layout + ",nomask,outs" + (",IL" if desc.get("flags") else "") + "> (variant " + os.environ.get("FK_FAST_VARIANT", "0") + ")", "kernel_ms": kernel_ms,
+                             "algorithmic_bytes_per_launch": alg_bytes},
+                # the same launch on two plain torch allocations (no placement): what the 55-pair probe of `placement` buys on this box
+                "value_unplaced": float(N) * T / (placement_info["two_arrays_ms"] * 1e-3) * world,
+                "parity_max_rel_vs_oracle": worst, "parity_tracks": int(len(sample)),
+                "gpu_clocks": gpu_clocks(), "hbm_probes": hbm_probes(device), "under_load": clocks_under_load(lambda: step(0, None, False)),   # rank 0 alone: no collective in the burst
+            })
         if per_rank is not None:
             out["per_rank"] = per_rank
         if exchange:
@@ -705,7 +758,7 @@ def main():
                                "double-buffered x / gathered" % (x.numel() * 8 // 1000000))
         if args.force_dist:
             out["dist_forced"] = f"{world}-rank {dist.get_backend()} group: init_process_group(device_id), all_gather_into_tensor, barrier, all_reduce(MAX) executed"
-        if world == 1 and args.placement in ("interleave", "none") and not os.environ.get("FK_BENCH_SKIP_PROBE"):
+        if args.full and world == 1 and args.placement in ("interleave", "none") and not os.environ.get("FK_BENCH_SKIP_PROBE"):
             # the third arrangement (two arrays placed by measurement), timed AFTER the measurement, for the record only
             try:
                 del covs, covs_p, got
@@ -722,12 +775,12 @@ def main():
                 torch.cuda.empty_cache()
             except Exception as exc:
                 out["placement"]["probe_error"] = repr(exc)[:200]
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             # the CPU baseline filters the same measurements: the first 64 x 256 tracks of the timed z buffer
             kc = min(N, CPU_TRACKS_PER_PROC * 256)
             zc = (z[:, :kc] if layout == "aos" else z[:, :, :kc].transpose(1, 2)).cpu().numpy()
             out["cpu_baseline"] = cpu_baseline(np.ascontiguousarray(zc), args.cpu_seconds, args.cpu_procs or None)
-        if world == 1 and not args.no_configs:
+        if args.full and world == 1 and not args.no_configs:
             out["configs"] = baseline_configs(args.config_reps)
         print(json.dumps(out), flush=True)
     parallel.shutdown()

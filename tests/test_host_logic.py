@@ -607,8 +607,25 @@ def test_engine_wrappers_hand_every_operand_to_the_parameter_of_its_name(monkeyp
     assert checked > 150
 
 
+def test_bench_dump_sample_is_fixed_and_small(tmp_path):
+    """bench.py --dump-outputs: the same tracks on every run with the same arguments, all of them distinct and in range, and
+    the four outputs of the headline shape (T = 100, (4, 2)) for those tracks under 64 MB, written as float64 .npy files."""
+    import bench
+    for N in (1_000_000, 250_000, 5000, 1000):
+        s = bench.dump_sample(N)
+        assert np.array_equal(s, bench.dump_sample(N)) and len(np.unique(s)) == len(s) == min(N, bench.DUMP_TRACKS)
+        assert s.min() >= 0 and s.max() < N
+    assert bench.DUMP_TRACKS * 100 * 8 * (4 + 16 + 4 + 16) < 64e6
+    s = bench.dump_sample(5000)
+    got = [np.ones((3, len(s), 4)), np.ones((3, len(s), 4, 4)), np.zeros((3, len(s), 4)), np.zeros((3, len(s), 4, 4))]
+    bench.dump_outputs(str(tmp_path / "d"), s, got)
+    for name, a in zip(("means", "covs", "means_p", "covs_p", "tracks"), got + [s]):
+        b = np.load(tmp_path / "d" / (name + ".npy"))
+        assert b.dtype == np.float64 and np.array_equal(b, a)
+
+
 def test_committed_bench_line_keeps_the_drivers_contract():
-    """profiles/r06/bench_default.json is a line bench.py printed on an MI355X: it carries every key the driver's contract names
+    """profiles/r06/bench_default.json is a line `bench.py --full` printed on an MI355X: it carries every key the driver's contract names
     (metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data /
     config.workload, the roofline object and the cpu_baseline object), its numbers are consistent with one another (value =
     units / time, roofline.achieved = algorithmic bytes / kernel time, frac = achieved / peak, kernel time <= step time), the

@@ -10,12 +10,12 @@ echo "headline kernel on this box: $MS ms"
 bash tools/gpu_scripts/box_state.sh > $O/box_state.txt 2>&1
 # every box: the same counters and track counts, so that a slow and a fast box can be laid side by side
 # is it the SHAPE (4,2) -- records of 32 / 128 bytes -- or the track count / the addresses?  other track counts, and (4,2) through bench_configs
-for n in 999936 1048576 1003520 500000; do timeout 100 python bench.py --steps 10 --warmup 3 --no-cpu --tracks $n 2>/dev/null | python -c "
+for n in 999936 1048576 1003520 500000; do timeout 100 python bench.py --full --steps 10 --warmup 3 --no-cpu --tracks $n 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline()); print(json.dumps({'tracks': $n, 'kernel_ms': d['roofline']['kernel_ms'], 'frac': d['roofline']['frac']}))" >> $O/slow_tracks.jsonl; done
 cat $O/slow_tracks.jsonl
 # the same workload with the output arrays placed differently in HBM, with the 3-wave variant, with the XCD swizzle
-for kv in FK_BENCH_PAD_MB=0 FK_BENCH_PAD_MB=37 FK_BENCH_PAD_MB=1001 FK_FAST_VARIANT=1 FK_FAST_XCD=1; do env $kv timeout 100 python bench.py --steps 10 --warmup 3 --no-cpu 2>/dev/null | python -c "
+for kv in FK_BENCH_PAD_MB=0 FK_BENCH_PAD_MB=37 FK_BENCH_PAD_MB=1001 FK_FAST_VARIANT=1 FK_FAST_XCD=1; do env $kv timeout 100 python bench.py --full --steps 10 --warmup 3 --no-cpu 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline()); print(json.dumps({'knob': '$kv', 'kernel_ms': d['roofline']['kernel_ms'], 'frac': d['roofline']['frac']}))" >> $O/slow_knobs.jsonl; done
 cat $O/slow_knobs.jsonl
@@ -29,8 +29,8 @@ python tools/pmc_summary.py $O/slow_sq $O/slow_tc $O/slow_tcc > $O/slow_pmc_summ
 find $O -name "*counter_collection.csv" -size +1M -delete
 if python -c "import sys; sys.exit(0 if float('$MS') > 5.9 else 1)"; then
   echo "SLOW BOX: probing"
-  timeout 200 python bench.py --steps 20 --warmup 5 --no-cpu --layout soa > $O/slow_bench_soa.json 2>/dev/null
-  timeout 200 python bench.py --steps 20 --warmup 5 --no-cpu --tracks 250000 > $O/slow_bench_quarter.json 2>/dev/null
+  timeout 200 python bench.py --full --steps 20 --warmup 5 --no-cpu --layout soa > $O/slow_bench_soa.json 2>/dev/null
+  timeout 200 python bench.py --full --steps 20 --warmup 5 --no-cpu --tracks 250000 > $O/slow_bench_quarter.json 2>/dev/null
   timeout 300 python tools/bench_configs.py --configs 3a --layouts soa,aos 2>/dev/null | grep "^{" > $O/slow_configs.jsonl
   timeout 120 python tools/bench_resample.py --shapes 125x8000000,1000x8000 --iters 10 2>/dev/null | grep "^{" > $O/slow_resample.jsonl
   python - <<PY
