@@ -179,6 +179,15 @@ def kf_rts(desc_kw, F, Q, Xs, Ps, xs, Ps_out, K, Pp, *, convention=0, status=Non
     _abi.check(rc, "fk_kf_rts_f64")
 
 
+def fls_batch(desc_kw, lag, k0, F, Q, H, R, z, x, P, xs, xhat, *, B=None, u=None, y=None, S=None, status=None):
+    """fk_fls_batch_f64: steps k0 .. k0+T-1 of the fixed-lag smoother.  xs holds the W = min(max(lag, 1) - 1, k0) pending rows
+    of the previous call in front of this call's T rows (include/filterhip.h)."""
+    d = fk_kf_desc(**desc_kw)
+    rc = _abi.lib().fk_fls_batch_f64(d, int(lag), int(k0), _ptr(F), _ptr(Q), _ptr(H), _ptr(R), _ptr(B), _ptr(u), _ptr(z),
+                                     _ptr(x), _ptr(P), _ptr(xs), _ptr(xhat), _ptr(y), _ptr(S), _ptr(status), _stream())
+    _abi.check(rc, "fk_fls_batch_f64")
+
+
 def ut_sigma_points(n, N, layout, scale, x, P, sigmas, status=None):
     rc = _abi.lib().fk_ut_sigma_points_f64(n, N, LAYOUTS[layout], float(scale), _ptr(x), _ptr(P),
                                            _ptr(sigmas), _ptr(status), _stream())

@@ -208,6 +208,27 @@ int fk_kf_rts_f64(const fk_kf_desc *desc, const double *F, const double *Q,
                   double *xs, double *Ps_out, double *K, double *Pp,
                   int32_t index_convention, int32_t *status, void *stream);
 
+/* FixedLagSmoother.smooth_batch / smooth (filterpy/kalman/fixed_lag_smoother.py:133-311) for N independent tracks: steps
+ * k = k0 .. k0+T-1 of the fixed-lag smoother of lag `lag`, the whole time loop in one launch.  Per step: x_pre = F x (+ B u),
+ * P = F P F' + Q, the Joseph-form update of fk_kf_batch_filter_f64; xhat[k] = x; xs[k] starts as x_pre; for k >= lag the
+ * rows k-i, i < lag, gain P ((F - K H)')^i H' S^-1 y (P the posterior; the reference's PS_i H'SI y, reassociated); for
+ * k < lag, xs[k] = x.  lag <= 0 therefore returns the priors, lag >= k0+T the filtered states.
+ *   desc    : n (1..16), m (1..8), nu (>= 0), N, T, layout; model_mode FK_MODEL_SHARED, update_first 0, alpha_sq 1,
+ *             flags 0 or FK_KF_FLAG_R_JOSEPH_DIAG -- anything else is FK_ERR_UNSUPPORTED.
+ *   F,Q [n*n], H [m*n], R [m*m], B [n*nu] (NULL when nu == 0) shared;  u [T][N][nu], z [T][N][m] records in `layout`.
+ *   x, P    : in: the state before step k0; out: after step k0+T-1.
+ *   xs      : [W + T][N][n] in/out, W = min(max(lag, 1) - 1, k0): the first W rows are the rows k0-W .. k0-1 that are still
+ *             pending on entry (a previous call's tail), then the T rows of this call.  Every row is written once; on
+ *             return the last min(max(lag, 1) - 1, k0+T) rows are the pending window of the next call.
+ *   xhat    : [T][N][n] the filtered states.   y [N][m], S [N][m*m]: the last step's, or NULL.   status [N] or NULL.
+ * Which kernel runs depends on (n, m, lag, layout) only, so a run split into chained calls is bit-identical to one call.
+ * S^-1 y comes from the LDL^T factorisation of kf_update (FK_STATUS_NOT_PD when S is not positive definite). */
+int fk_fls_batch_f64(const fk_kf_desc *desc, int32_t lag, int64_t k0,
+                     const double *F, const double *Q, const double *H, const double *R,
+                     const double *B, const double *u, const double *z,
+                     double *x, double *P, double *xs, double *xhat,
+                     double *y, double *S, int32_t *status, void *stream);
+
 /* ------------------------------------------------------------------ */
 /* Unscented transform path                                           */
 /* ------------------------------------------------------------------ */
