@@ -37,12 +37,18 @@ def _lag_update(rows, k, N, P, H, SI, K, F, y):
 
 def smooth_batch(x, P, zs, N, F, Q, H, R, B=0., us=None):
     """fixed_lag_smoother.py:217-311 (x 1-D or a column, as the reference takes it)"""
+    return smooth_batch_state(x, P, zs, N, F, Q, H, R, B, us)[:2]
+
+
+def smooth_batch_state(x, P, zs, N, F, Q, H, R, B=0., us=None):
+    """smooth_batch, plus the state after the last step: (xSmooth, xhat, x, P, y, S)"""
     x = np.asarray(x, dtype=float)
     n = x.shape[0]
     I = np.eye(n)
     T = len(zs)
     xSmooth = np.zeros((T,) + x.shape)
     xhat = np.zeros((T,) + x.shape)
+    y = S = None
     for k, z in enumerate(zs):
         x_pre, x, P, y, S, SI, K = _step(x, P, z, F, Q, H, R, B, None if us is None else us[k], I)
         xhat[k] = x.copy()
@@ -51,7 +57,7 @@ def smooth_batch(x, P, zs, N, F, Q, H, R, B=0., us=None):
             _lag_update(xSmooth, k, N, P, H, SI, K, F, y)
         else:
             xSmooth[k] = xhat[k]
-    return xSmooth, xhat
+    return xSmooth, xhat, x, P, y, S
 
 
 class SmoothPort:

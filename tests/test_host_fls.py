@@ -10,7 +10,8 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import ROOT, golden, rel_err_rows
+from conftest import ROOT, golden, rel_err, rel_err_rows
+import fls_hp
 import fls_port
 from filterpy_amd.kalman import FixedLagSmoother, FixedLagSmootherBank
 
@@ -96,12 +97,21 @@ def test_port_matches_live_reference_on_random_cases():
 HC_SRC = r'''
 #include "fk_fls.hpp"
 using namespace fk;
-constexpr int NX = 16, NZ = 8, LMAX = 24;
-// one track through fls_step on a padded (16, 8) register model, the shift register's rows written out as the kernel does
+// the register shapes: -DHC_NX/-DHC_NZ/-DHC_LMAX builds one entry of fk_dims_fls.def at its exact dims; the default is a padded
+// (16, 8) model that serves every golden case
+#ifndef HC_NX
+#define HC_NX 16
+#define HC_NZ 8
+#define HC_LMAX 24
+#endif
+constexpr int NX = HC_NX, NZ = HC_NZ, LMAX = HC_LMAX;
+// one track through fls_step, the shift register's rows written out as the kernel does.  Pout, yout, Sout (NULL: not
+// wanted) receive the final P and the last step's y and S.
 extern "C" int hc_fls(int n, int m, int lag, long T, const double *F, const double *Q, const double *H, const double *R,
                       int nu, const double *B, const double *us, const double *zs, int rj, double *x0, double *P0,
-                      double *xs, double *xhat)
+                      double *xs, double *xhat, double *Pout, double *yout, double *Sout)
 {
+    if (n > NX || m > NZ) return -1;
     RegModel<NX, NZ> M;
     for (int i = 0; i < NX; ++i) for (int j = 0; j < NX; ++j) {
         M.F[i * NX + j] = (i < n && j < n) ? F[i * n + j] : (i == j);
@@ -129,9 +139,18 @@ extern "C" int hc_fls(int n, int m, int lag, long T, const double *F, const doub
     const long W = Lf - 1 < T ? Lf - 1 : T;
     for (long r = 0; r < W; ++r) for (int i = 0; i < n; ++i) xs[(T - 1 - r) * n + i] = pend[r * NX + i];
     for (int i = 0; i < n; ++i) x0[i] = x[i];
+    if (Pout) for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) Pout[i * n + j] = P[i * NX + j];
+    if (yout) for (int i = 0; i < m; ++i) yout[i] = y[i];
+    if (Sout) for (int i = 0; i < m; ++i) for (int j = 0; j < m; ++j) Sout[i * m + j] = S[i * NZ + j];
     return st;
 }
 '''
+
+
+def _hc_cmd(src, so, dims=None):
+    d = [] if dims is None else ["-DHC_NX=%d" % dims[0], "-DHC_NZ=%d" % dims[1], "-DHC_LMAX=%d" % dims[2]]
+    return ["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=on", "-w", *d,
+            "-I", os.path.join(ROOT, "filterpy_amd", "csrc"), str(src), "-o", str(so)]
 
 
 @pytest.fixture(scope="module")
@@ -139,8 +158,7 @@ def hc(tmp_path_factory):
     d = tmp_path_factory.mktemp("hc_fls")
     src, so = d / "hc_fls.cpp", d / "libhc_fls.so"
     src.write_text(HC_SRC)
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=on", "-w",
-                           "-I", os.path.join(ROOT, "filterpy_amd", "csrc"), str(src), "-o", str(so)])
+    subprocess.check_call(_hc_cmd(src, so))
     return ctypes.CDLL(str(so))
 
 
@@ -171,10 +189,165 @@ def test_host_step_matches_golden(hc, ci):
     nu = 0 if B is None else B.shape[1]
     st = hc.hc_fls(n, m, lag, ctypes.c_long(T), _p(cc(c["F"])), _p(cc(Q)), _p(cc(c["H"])), _p(cc(R)), nu,
                    _p(None if B is None else cc(B)), _p(None if us is None else cc(us)), _p(cc(c["zs"])), rj,
-                   _p(x0), _p(cc(c["P0"])), _p(xs), _p(xhat))
+                   _p(x0), _p(cc(c["P0"])), _p(xs), _p(xhat), None, None, None)
     assert st == 0
     assert rel_err_rows(xs, c["xs"].reshape(T, n)) <= 1e-12
     assert rel_err_rows(xhat, c["xhat"].reshape(T, n)) <= 1e-12
+
+
+# ---- tests/fls_hp.py, the extended-precision truth ------------------------------------------------------------------------
+def test_hp_is_extended_precision():
+    assert fls_hp.LD is np.longdouble and np.finfo(fls_hp.LD).eps < 1e-18
+    one = fls_hp.ld(1.0)
+    assert one + fls_hp.ld(2.0 ** -60) != one
+    S = fls_hp.ld([[[0.0, 2.0, 1.0], [1.0, 1e-3, 0.0], [3.0, 1.0, 7.0]]])     # a zero pivot: needs the row exchange
+    E = fls_hp.inv(S) @ S - np.eye(3, dtype=fls_hp.LD)
+    assert fls_hp.inv(S).dtype == fls_hp.LD and float(np.max(np.abs(E))) < 1e-17
+
+
+@pytest.mark.parametrize("ci", range(NC))
+def test_hp_matches_golden(ci):
+    c = case(ci)
+    n, m, T = c["n"], c["m"], c["zs"].shape[0]
+    B, us = c.get("B"), None
+    if "us" in c:
+        us = c["us"].reshape(T, 1, -1)
+    h = fls_hp.smooth_batch(c["x0"].reshape(1, n), c["P0"][None], c["zs"].reshape(T, 1, m), c["lag"], c["F"], c["Q"], c["H"],
+                            c["R"], B=B, us=us)
+    # normwise over the run: a row that cancels (case 17: 0.09 after rows of 27) carries the golden's float64 error, 2e-12 of it
+    assert rel_err(h["xs"][:, 0].astype(float), c["xs"].reshape(T, n)) <= 1e-12
+    assert rel_err(h["xhat"][:, 0].astype(float), c["xhat"].reshape(T, n)) <= 1e-12
+
+
+def _mp_smooth(x0, P0, zs, lag, F, Q, H, R, B=None, us=None):
+    """the reference's smooth_batch once more, in mpmath at 40 digits (scalar R: numpy's rule)"""
+    import mpmath as mp
+    M = lambda a: mp.matrix([[mp.mpf(float(v)) for v in row] for row in np.atleast_2d(a)])     # noqa: E731
+    col = lambda v: mp.matrix([mp.mpf(float(e)) for e in np.ravel(v)])                          # noqa: E731
+    n, m = len(x0), zs.shape[1]
+    F, Q, H = M(F), M(Q), M(H)
+    Rm = mp.matrix(m, m) + mp.mpf(float(R)) if np.ndim(R) == 0 else M(R)
+    KR_scalar = np.ndim(R) == 0
+    if KR_scalar:
+        Rm = mp.matrix([[mp.mpf(float(R))] * m for _ in range(m)])
+    x, P, I = col(x0), M(P0), mp.eye(n)
+    rows, xhat = [], []
+    for k in range(zs.shape[0]):
+        x_pre = F * x
+        if us is not None:
+            x_pre = x_pre + (mp.mpf(float(B)) * col(us[k]) if np.ndim(B) == 0 else M(B) * col(us[k]))
+        P = F * P * F.T + Q
+        y = col(zs[k]) - H * x_pre
+        S = H * P * H.T + Rm
+        SI = mp.inverse(S)
+        K = P * H.T * SI
+        x = x_pre + K * y
+        IKH = I - K * H
+        P = IKH * P * IKH.T + (mp.mpf(float(R)) * K * K.T if KR_scalar else K * Rm * K.T)
+        xhat.append(x)
+        rows.append(x_pre)
+        if k >= lag:
+            PS, FLH = P, (F - K * H).T
+            for i in range(lag):
+                rows[k - i] = rows[k - i] + PS * H.T * SI * y
+                PS = PS * FLH
+        else:
+            rows[k] = x
+    to = lambda vs: np.array([[float(e) for e in v] for v in vs])        # noqa: E731
+    exact = lambda vs: [[e for e in v] for v in vs]                       # noqa: E731
+    return exact(rows), exact(xhat), to(rows)
+
+
+def _mpf_ld(v):
+    """a longdouble exactly: its 64-bit significand is the sum of two doubles"""
+    import mpmath as mp
+    hi = float(v)
+    return mp.mpf(hi) + mp.mpf(float(v - fls_hp.ld(hi)))
+
+
+@pytest.mark.parametrize("n,m,lag,T,ctrl,scalar_R", [(1, 1, 2, 8, 0, 0), (2, 1, 3, 8, 1, 0), (3, 2, 2, 7, 0, 1),
+                                                     (3, 3, 8, 6, 1, 0), (2, 2, 0, 5, 0, 0), (3, 1, -1, 4, 1, 1)])
+def test_hp_matches_mpmath(n, m, lag, T, ctrl, scalar_R):
+    import mpmath as mp
+    mp.mp.dps = 40
+    d = fls_hp.random_model(n, m, 1, T, 100 * n + 10 * m + lag, nu=2 if ctrl else 0, scalar_R=bool(scalar_R))
+    if ctrl and n == 3 and m == 1:
+        d["B"] = 0.5                                        # a scalar B: b u
+        d["us"] = np.random.RandomState(1).randn(T, 1, n)
+    us = None if d["us"] is None else d["us"][:, 0]
+    rows, xhat, _ = _mp_smooth(d["x0"][0], d["P0"][0], d["zs"][:, 0], lag, d["F"], d["Q"], d["H"], d["R"], d["B"], us)
+    h = fls_hp.smooth_batch(d["x0"], d["P0"], d["zs"], lag, d["F"], d["Q"], d["H"], d["R"], B=d["B"], us=d["us"])
+    for name, ref in (("xs", rows), ("xhat", xhat)):
+        for k in range(T):
+            scale = max(abs(e) for e in ref[k])
+            err = max(abs(_mpf_ld(h[name][k, 0, i]) - ref[k][i]) for i in range(n)) / scale
+            assert err <= 1e-17, (name, k, float(err))
+
+
+# ---- fk_fls.hpp at the exact shapes of fk_dims_fls.def, against tests/fls_hp.py ----------------------------------------------
+ENTRIES = fls_hp.fast_entries()
+_EXERCISED = set()
+
+
+@pytest.fixture(scope="module")
+def hc_exact(tmp_path_factory):
+    """one host build of hc_fls per FK_FLS_INST entry (compiled side by side)"""
+    from concurrent.futures import ThreadPoolExecutor
+    d = tmp_path_factory.mktemp("hc_fls_exact")
+    src = d / "hc_fls.cpp"
+    src.write_text(HC_SRC)
+    sos = {e: d / ("libhc_fls_%d_%d_%d.so" % e) for e in ENTRIES}
+    with ThreadPoolExecutor(max(1, min(8, len(os.sched_getaffinity(0))))) as ex:
+        list(ex.map(lambda e: subprocess.check_call(_hc_cmd(src, sos[e], e)), ENTRIES))
+    return {e: ctypes.CDLL(str(so)) for e, so in sos.items()}
+
+
+def _hc_run(lib, d, lag, T):
+    """track 0 of model d, first T steps, through one hc_fls build -> the outputs as fls_port / fls_hp name them"""
+    cc = lambda a: np.ascontiguousarray(a, dtype=float)      # noqa: E731
+    n, m = d["F"].shape[0], d["H"].shape[0]
+    scalar_R = np.ndim(d["R"]) == 0
+    R = np.full((m, m), d["R"]) if scalar_R else d["R"]
+    nu = 0 if d["B"] is None else d["B"].shape[1]
+    x, P0 = cc(d["x0"][0]).copy(), cc(d["P0"][0])
+    o = dict(xs=np.zeros((T, n)), xhat=np.zeros((T, n)), P=np.zeros((n, n)), y=np.zeros(m), S=np.zeros((m, m)))
+    st = lib.hc_fls(n, m, lag, ctypes.c_long(T), _p(cc(d["F"])), _p(cc(d["Q"])), _p(cc(d["H"])), _p(cc(R)), nu,
+                    _p(None if nu == 0 else cc(d["B"])), _p(None if nu == 0 else cc(d["us"][:T, 0])), _p(cc(d["zs"][:T, 0])),
+                    int(scalar_R and m > 1), _p(x), _p(P0), _p(o["xs"]), _p(o["xhat"]), _p(o["P"]), _p(o["y"]), _p(o["S"]))
+    o["x"] = x
+    return st, o
+
+
+def check_exact_entry(lib, e):
+    nx, nz, L = e
+    for variant in ("plain", "control", "scalar_R"):
+        seed = 1000 * nx + 100 * nz + L + {"plain": 0, "control": 1, "scalar_R": 2}[variant]
+        d = fls_hp.random_model(nx, nz, 1, 2 * L + 3, seed, nu=2 if variant == "control" else 0,
+                                scalar_R=variant == "scalar_R")
+        for lag in (-2, 0, 1, 2, L - 1, L):
+            for T in (1, L - 1, 2 * L + 3):
+                st, got = _hc_run(lib, d, lag, T)
+                assert st == 0
+                us = None if d["us"] is None else d["us"][:T]
+                port = dict(zip(("xs", "xhat", "x", "P", "y", "S"),
+                                fls_port.smooth_batch_state(d["x0"][0], d["P0"][0], d["zs"][:T, 0], lag, d["F"], d["Q"],
+                                                            d["H"], d["R"], d["B"], None if us is None else us[:, 0])))
+                hp = fls_hp.smooth_batch(d["x0"], d["P0"], d["zs"][:T], lag, d["F"], d["Q"], d["H"], d["R"], B=d["B"], us=us)
+                fls_hp.compare_track(f"host {e} {variant} lag {lag} T {T}", got, port, hp, family="host exact shapes")
+    _EXERCISED.add(e)
+
+
+@pytest.mark.parametrize("e", ENTRIES, ids=lambda e: "%d_%d_%d" % e)
+def test_host_step_exact_shape_vs_hp(hc_exact, e):
+    check_exact_entry(hc_exact[e], e)
+
+
+def test_host_every_def_entry_exercised(hc_exact):
+    assert len(ENTRIES) >= 16 and len(set(ENTRIES)) == len(ENTRIES)
+    for e in ENTRIES:                          # (run alone, or under a -k that skipped some: exercise the rest here)
+        if e not in _EXERCISED:
+            check_exact_entry(hc_exact[e], e)
+    assert _EXERCISED == set(ENTRIES)
 
 
 # ---- the drop-in layer on a stand-in engine -----------------------------------------------------------------------------
