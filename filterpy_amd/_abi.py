@@ -69,6 +69,9 @@ SIGNATURES = {
     "fk_kf_update_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 12),
     "fk_kf_rts_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 8 + [c_i32, c_vp, c_vp]),
     "fk_fls_batch_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc), c_i32, c_i64] + [c_vp] * 15),
+    "fk_srkf_batch_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 20),
+    "fk_srkf_predict_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 8),
+    "fk_srkf_update_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 12),
     "fk_ut_sigma_points_f64": (ctypes.c_int, [c_i32, c_i64, c_i32, c_f64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "fk_ut_transform_f64": (ctypes.c_int, [c_i32, c_i32, c_i64, c_i32] + [c_vp] * 7),
     "fk_ut_cross_variance_f64": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i64, c_i32] + [c_vp] * 7),

@@ -188,6 +188,31 @@ def fls_batch(desc_kw, lag, k0, F, Q, H, R, z, x, P, xs, xhat, *, B=None, u=None
     _abi.check(rc, "fk_fls_batch_f64")
 
 
+def srkf_batch(desc_kw, F, Q12, H, R12, z, x, P12, *, B=None, u=None, mask=None, means=None, covs=None, means_p=None,
+               covs_p=None, y=None, K=None, S12=None, SI12=None, status=None):
+    """fk_srkf_batch_f64: T steps of the square-root filter (factors in and out; include/filterhip.h)."""
+    _keep = []
+    d = fk_kf_desc(**desc_kw)
+    rc = _abi.lib().fk_srkf_batch_f64(d, _ptr(F), _ptr(Q12), _ptr(H), _ptr(R12), _ptr(B), _ptr(u), _ptr(z),
+                                      _mask_ptr(mask, _keep), _ptr(x), _ptr(P12), _ptr(means), _ptr(covs), _ptr(means_p),
+                                      _ptr(covs_p), _ptr(y), _ptr(K), _ptr(S12), _ptr(SI12), _ptr(status), _stream())
+    _abi.check(rc, "fk_srkf_batch_f64")
+
+
+def srkf_predict(desc_kw, F, Q12, x, P12, *, B=None, u=None, status=None):
+    d = fk_kf_desc(**desc_kw)
+    rc = _abi.lib().fk_srkf_predict_f64(d, _ptr(F), _ptr(Q12), _ptr(B), _ptr(u), _ptr(x), _ptr(P12), _ptr(status), _stream())
+    _abi.check(rc, "fk_srkf_predict_f64")
+
+
+def srkf_update(desc_kw, H, R12, z, x, P12, *, mask=None, y=None, K=None, S12=None, SI12=None, status=None):
+    _keep = []
+    d = fk_kf_desc(**desc_kw)
+    rc = _abi.lib().fk_srkf_update_f64(d, _ptr(H), _ptr(R12), _ptr(z), _mask_ptr(mask, _keep), _ptr(x), _ptr(P12), _ptr(y),
+                                       _ptr(K), _ptr(S12), _ptr(SI12), _ptr(status), _stream())
+    _abi.check(rc, "fk_srkf_update_f64")
+
+
 def ut_sigma_points(n, N, layout, scale, x, P, sigmas, status=None):
     rc = _abi.lib().fk_ut_sigma_points_f64(n, N, LAYOUTS[layout], float(scale), _ptr(x), _ptr(P),
                                            _ptr(sigmas), _ptr(status), _stream())

@@ -3,6 +3,7 @@ re-exports everything; here only what the engine implements)."""
 from .kalman_filter import (KalmanFilter, KalmanFilterBank, predict, update, batch_filter,  # noqa: F401
                             rts_smoother, predict_steadystate, update_steadystate)
 from .fixed_lag_smoother import FixedLagSmoother, FixedLagSmootherBank  # noqa: F401
+from .square_root import SquareRootKalmanFilter, SquareRootKalmanFilterBank  # noqa: F401
 from .sigma_points import MerweScaledSigmaPoints, JulierSigmaPoints  # noqa: F401
 from .unscented_transform import unscented_transform  # noqa: F401
 from .UKF import UnscentedKalmanFilter  # noqa: F401

@@ -229,6 +229,45 @@ int fk_fls_batch_f64(const fk_kf_desc *desc, int32_t lag, int64_t k0,
                      double *x, double *P, double *xs, double *xhat,
                      double *y, double *S, int32_t *status, void *stream);
 
+/* SquareRootKalmanFilter (filterpy/kalman/square_root.py:172-248) for N independent filters.  P, Q and R are carried as their
+ * lower-triangular factors P1_2, Q1_2, R1_2 (P = P1_2 P1_2'); P is never formed.  Per step:
+ *   predict (:226-248)  x = F x (+ B u);  R = qr([F P1_2, Q1_2]');  P1_2 = R[:n, :n]'
+ *   update  (:172-224)  M = [[R1_2', 0], [(H P1_2)', P1_2']];  r = qr(M);  S1_2 = r[:m, :m]';  SI1_2 = S1_2^-1 (the reference's
+ *                       pinv);  K = r[:m, m:]' SI1_2;  y = z - H x;  x += K y;  P1_2 = r[m:, m:]'
+ * Each QR is Householder's in LAPACK's convention (scipy.linalg.qr = dgeqrf / dgeqr2 / dlarfg): every diagonal entry of R is
+ * -sign(alpha) |column| except where nothing is reflected -- a sub-column below alpha that is exactly zero, and the last column
+ * of the square M -- so S1_2 and P1_2 carry the reference's signs (usually negative diagonals).
+ *   desc      : n (1..16), m (1..8), nu (>= 0), N, T, layout, update_first (nonzero: update, then predict, as
+ *               kalman_filter.py:966-978); model_mode FK_MODEL_SHARED, alpha_sq 1, flags 0 -- anything else FK_ERR_UNSUPPORTED.
+ *   F [n*n], Q1_2 [n*n], H [m*n], R1_2 [m*m], B [n*nu] (NULL when nu == 0): shared.  Q1_2, R1_2 (and P1_2) are LOWER triangular
+ *               factors (the reference's setters store cholesky(., lower=True), :274-340); their upper triangles are not read.
+ *   u [T][N][nu], z [T][N][m]: records in `layout`.   mask: uint8 [T][N] (t-major), 0 = no measurement (the reference's
+ *               update(None), :189-193: x and P1_2 unchanged); NULL = every step updates.
+ *   x [N][n], P1_2 [N][n*n]: in: the state before the first step; out: after the last.
+ *   means, sqrt_covs     : posterior per step [T][N][n] / [T][N][n*n]; means_p, sqrt_covs_p: prior per step.  Each may be NULL
+ *               (not stored).  The factor records are full n x n, the upper triangle written as zeros.
+ *   y [N][m], K [N][n*m], S1_2 [N][m*m], SI1_2 [N][m*m]: the values of the LAST update of the call (the attributes :207-217), or
+ *               NULL; a track that does not update in the call leaves them as they were.
+ *   status [N] or NULL: FK_STATUS_NOT_PD when a diagonal entry of S1_2 is at or below m eps max|diag S1_2| (a cheap stand-in for
+ *               pinv's cutoff: the reference would go on with a pseudo-inverse), FK_STATUS_NONFINITE.
+ * Which kernel runs depends on (n, m, layout) only, so a run split into chained calls is bit-identical to one call. */
+int fk_srkf_batch_f64(const fk_kf_desc *desc, const double *F, const double *Q1_2, const double *H, const double *R1_2,
+                      const double *B, const double *u, const double *z, const uint8_t *mask,
+                      double *x, double *P1_2, double *means, double *sqrt_covs, double *means_p, double *sqrt_covs_p,
+                      double *y, double *K, double *S1_2, double *SI1_2, int32_t *status, void *stream);
+
+/* SquareRootKalmanFilter.predict (square_root.py:226-248) on a resident batch: one step, x / P1_2 [N][n*n] in place.
+ * u [N][nu] (NULL when nu == 0).  desc->T is ignored (treated as 1); the rest of desc as for fk_srkf_batch_f64. */
+int fk_srkf_predict_f64(const fk_kf_desc *desc, const double *F, const double *Q1_2, const double *B, const double *u,
+                        double *x, double *P1_2, int32_t *status, void *stream);
+
+/* SquareRootKalmanFilter.update (square_root.py:172-224) on a resident batch: one step, x / P1_2 in place; z [N][m],
+ * mask [N] (or NULL), R1_2 the factor to use (the reference's R2 argument or its _R1_2).  y, K, S1_2, SI1_2 as for
+ * fk_srkf_batch_f64.  desc->T is ignored (treated as 1). */
+int fk_srkf_update_f64(const fk_kf_desc *desc, const double *H, const double *R1_2, const double *z, const uint8_t *mask,
+                       double *x, double *P1_2, double *y, double *K, double *S1_2, double *SI1_2,
+                       int32_t *status, void *stream);
+
 /* ------------------------------------------------------------------ */
 /* Unscented transform path                                           */
 /* ------------------------------------------------------------------ */
