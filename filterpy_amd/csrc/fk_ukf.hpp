@@ -21,19 +21,46 @@
 namespace fk {
 
 // sqrt(d) and 1 / sqrt(d) together; 1 / d.  On the device: the v_rsq_f64 / v_rcp_f64 seeds (2^-24 relative, measured:
-// tools/experiments/rsq_seed_accuracy.hip, profiles/r03/rsq_seed_accuracy.jsonl) refined by ONE Goldschmidt / Newton step:
-// 4e-15 / 2e-15 relative, 7 / 3 instructions (the compiler's correctly-rounded sqrt followed by a correctly-rounded division
-// is ~28, with range scaling the pivots of a covariance factor do not need; a second step reaches 1e-16 and costs four more
-// instructions on the critical path of every column).  The factor feeds covariance sums without cancellation and a mean in
-// which the +l_k and -l_k terms cancel to first order, so its error arrives unamplified: far inside the 1e-10 bar.  A
-// non-positive or non-finite pivot yields NaN / inf like sqrt would; the caller's pivot test reports it (ST_NOT_PD).  On the
+// tools/experiments/rsq_seed_accuracy.hip, profiles/r03/rsq_seed_accuracy.jsonl) refined by TWO Goldschmidt / Newton steps:
+// rounding-limited (1e-16 relative), 10 / 5 instructions (the compiler's correctly-rounded sqrt followed by a correctly-rounded
+// division is ~28, with range scaling the pivots of a covariance factor do not need).
+// ONE step (4e-15 / 2e-15 at the seeds' worst, 10-20 ulps: what this file ran until the precision tests existed) leaves the
+// result at the mercy of the seed: a pivot's error is a backward error on P, amplified by cond(P) in every later pivot of every
+// later step.  Measured against the longdouble UKF of tests/ukf_hp.py on the ill-conditioned models of
+// tests/test_gpu_ukf_precision.py (P0 = 1e6 I, R = 1e-4 I; docs/MEASUREMENTS.md, "UKF precision"):
+//   on the host with float-rounded seeds (tests/test_host_ukf_hp.py), one step is 5.4x less accurate than the plain sqrt /
+//   division in the geometric mean over all outputs, up to 170x on one, and up to 44x the float64 oracle's own error -- 5.4x
+//   over the tests' bar; an exact residual correction of the root alone (s += (d - s s) h, the reciprocal left at 4e-15) still
+//   42x / 18x; two steps are indistinguishable from the plain operations (0.98x in the mean, every output inside the scatter of
+//   two float64 orderings);
+//   on the MI355X, whose seeds are typically much better than their 2^-24.2 maximum, one step passes the bar, at 0.84 of it
+//   (6x the oracle's median error on the stiff model at (4,2), 2-3x on benign models); two steps: 0.17 and 0.9-1.1x.
+// The second step costs nothing measurable (configs[3], (6,3): 0.834 -> 0.837 ms, +-4 % run to run).  On the benign models of
+// the other UKF tests the difference is 3e-15 against 1e-15 -- invisible at their 1e-10 bar, which is why nothing saw it.
+// A non-positive or non-finite pivot yields NaN / inf like sqrt would; the caller's pivot test reports it (ST_NOT_PD).  On the
 // host (tests/hostcheck): the plain operations.
+// FK_UKF_EMULATE_SEEDS (defined by the emulated-pivot host build of tests/test_host_ukf_hp.py, never by the library): the host
+// takes the DEVICE branch below with the exact result rounded to float as a stand-in for the instruction's seed, so that the
+// refinement lines -- the same text, not a copy -- are held to the precision bar on a CPU.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FK_UKF_SEEDED 1
+#define FK_RSQ_SEED(d) __builtin_amdgcn_rsq(d)
+#define FK_RCP_SEED(d) __builtin_amdgcn_rcp(d)
+#elif defined(FK_UKF_EMULATE_SEEDS)
+#define FK_UKF_SEEDED 1
+#define FK_RSQ_SEED(d) ((double)(float)(1.0 / sqrt(d)))
+#define FK_RCP_SEED(d) ((double)(float)(1.0 / (d)))
+#endif
+
 FK_HD void sqrt_rsqrt(double d, double &s, double &inv)
 {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const double y = __builtin_amdgcn_rsq(d);
-    double g = d * y, h = 0.5 * y;
-    const double r = fma(-h, g, 0.5);
+#if defined(FK_UKF_SEEDED)
+    const double y = FK_RSQ_SEED(d);
+    double g = d * y, h = 0.5 * y;                 // g -> sqrt(d), h -> 1 / (2 sqrt(d))
+    double r = fma(-h, g, 0.5);
+    g = fma(g, r, g);
+    h = fma(h, r, h);
+    r = fma(-h, g, 0.5);
     s = fma(g, r, g);
     h = fma(h, r, h);
     inv = h + h;
@@ -45,9 +72,11 @@ FK_HD void sqrt_rsqrt(double d, double &s, double &inv)
 
 FK_HD double rcp_refined(double d)
 {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const double r = __builtin_amdgcn_rcp(d);
-    const double e = fma(-d, r, 1.0);
+#if defined(FK_UKF_SEEDED)
+    double r = FK_RCP_SEED(d);
+    double e = fma(-d, r, 1.0);
+    r = fma(r, e, r);
+    e = fma(-d, r, 1.0);
     return fma(r, e, r);
 #else
     return 1.0 / d;

@@ -627,7 +627,7 @@ extern "C" int hc_ukf_linear_v3(int n, int m, long T, const double *F, const dou
                                 const unsigned char *mask, double *x0, double *P0, double *means, double *covs)
 {
 #define GO(NXV, NZV) if (n == NXV && m == NZV) return ukf_v3_batch<NXV, NZV>(T, F, H, Q, R, Wm, Wc, scale, zs, mask, x0, P0, means, covs)
-    GO(2, 2); GO(4, 2); GO(6, 3); GO(8, 4); GO(9, 3); GO(9, 4); GO(3, 1); GO(5, 2); GO(7, 3);
+    GO(2, 1); GO(2, 2); GO(4, 2); GO(6, 3); GO(8, 4); GO(9, 3); GO(9, 4); GO(3, 1); GO(5, 2); GO(7, 3);
 #undef GO
     return -1;
 }
@@ -648,7 +648,7 @@ extern "C" int hc_ukf_linear_v4(int n, int m, long T, const double *F, const dou
                                 const unsigned char *mask, double *x0, double *P0, double *means, double *covs)
 {
 #define GO(NXV, NZV) if (n == NXV && m == NZV) return ukf_v3_batch<NXV, NZV, true>(T, F, H, Q, R, Wm, Wc, scale, zs, mask, x0, P0, means, covs)
-    GO(2, 2); GO(4, 2); GO(6, 3); GO(8, 4); GO(9, 3); GO(9, 4); GO(3, 1); GO(5, 2); GO(7, 3);
+    GO(2, 1); GO(2, 2); GO(4, 2); GO(6, 3); GO(8, 4); GO(9, 3); GO(9, 4); GO(3, 1); GO(5, 2); GO(7, 3);
 #undef GO
     return -1;
 }
