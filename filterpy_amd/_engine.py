@@ -213,6 +213,31 @@ def srkf_update(desc_kw, H, R12, z, x, P12, *, mask=None, y=None, K=None, S12=No
     _abi.check(rc, "fk_srkf_update_f64")
 
 
+def info_batch(desc_kw, F, Q, H, Rinv, z, x, Pinv, *, B=None, u=None, mask=None, means=None, covs=None, means_p=None,
+               covs_p=None, status=None):
+    """fk_info_batch_f64: T steps of the information filter (x and P_inv in and out; include/filterhip.h)."""
+    _keep = []
+    d = fk_kf_desc(**desc_kw)
+    rc = _abi.lib().fk_info_batch_f64(d, _ptr(F), _ptr(Q), _ptr(H), _ptr(Rinv), _ptr(B), _ptr(u), _ptr(z),
+                                      _mask_ptr(mask, _keep), _ptr(x), _ptr(Pinv), _ptr(means), _ptr(covs), _ptr(means_p),
+                                      _ptr(covs_p), _ptr(status), _stream())
+    _abi.check(rc, "fk_info_batch_f64")
+
+
+def info_predict(desc_kw, F, Q, x, Pinv, *, B=None, u=None, status=None):
+    d = fk_kf_desc(**desc_kw)
+    rc = _abi.lib().fk_info_predict_f64(d, _ptr(F), _ptr(Q), _ptr(B), _ptr(u), _ptr(x), _ptr(Pinv), _ptr(status), _stream())
+    _abi.check(rc, "fk_info_predict_f64")
+
+
+def info_update(desc_kw, H, Rinv, z, x, Pinv, *, mask=None, y=None, K=None, status=None):
+    _keep = []
+    d = fk_kf_desc(**desc_kw)
+    rc = _abi.lib().fk_info_update_f64(d, _ptr(H), _ptr(Rinv), _ptr(z), _mask_ptr(mask, _keep), _ptr(x), _ptr(Pinv), _ptr(y),
+                                       _ptr(K), _ptr(status), _stream())
+    _abi.check(rc, "fk_info_update_f64")
+
+
 def ut_sigma_points(n, N, layout, scale, x, P, sigmas, status=None):
     rc = _abi.lib().fk_ut_sigma_points_f64(n, N, LAYOUTS[layout], float(scale), _ptr(x), _ptr(P),
                                            _ptr(sigmas), _ptr(status), _stream())

@@ -268,6 +268,41 @@ int fk_srkf_update_f64(const fk_kf_desc *desc, const double *H, const double *R1
                        double *x, double *P1_2, double *y, double *K, double *S1_2, double *SI1_2,
                        int32_t *status, void *stream);
 
+/* InformationFilter (filterpy/kalman/information_filter.py:178-289, the invertible branch) for N independent filters: the
+ * inverse-covariance form of the Kalman filter.  The state is x and P_inv, the measurement noise is given as R_inv.  Per step:
+ *   predict (:245-289)  x = F x (+ B u);  P_inv = inv(F inv(P_inv) F' + Q)   -- the reference's inv(inv(F^-T P_inv F^-1) + Q)
+ *   update  (:178-243)  y = z - H x;  P_inv += H' R_inv H (the reference's S);  x += inv(P_inv) H' R_inv y;
+ *                       K = inv(P_inv) H' R_inv
+ * Every inverse is an L D L' factorisation of a symmetric positive definite n x n matrix: two per step (the update's is reused
+ * by the predict that follows it), no F^-1.  The reference's _no_information branch (an exactly singular P_inv) is not ported.
+ *   desc      : n (1..16), m (1..8), nu (>= 0), N, T, layout, update_first (nonzero: update, then predict);
+ *               model_mode FK_MODEL_SHARED, alpha_sq 1, flags 0 -- anything else FK_ERR_UNSUPPORTED.
+ *   F [n*n], Q [n*n], H [m*n], R_inv [m*m], B [n*nu] (NULL when nu == 0): shared.
+ *   u [T][N][nu], z [T][N][m]: records in `layout`.   mask: uint8 [T][N] (t-major), 0 = no measurement (the reference's
+ *               update(None), :194-198: x and P_inv unchanged); NULL = every step updates.
+ *   x [N][n], P_inv [N][n*n]: in: the state before the first step; out: after the last.  P_inv is symmetric: its lower triangle
+ *               is read, records are written whole and exactly symmetric.
+ *   means, covs          : posterior x / P_inv per step [T][N][n] / [T][N][n*n]; means_p, covs_p: prior per step.  Each may be
+ *               NULL (not stored).
+ *   status [N] or NULL: FK_STATUS_NOT_PD when a pivot of a factorisation is at or below n eps max|diag| of the matrix being
+ *               factored (P_inv or F P F' + Q is singular; the state is then not meaningful), FK_STATUS_NONFINITE.
+ * Which kernel runs depends on (n, m, layout) only, so a run split into chained calls is bit-identical to one call. */
+int fk_info_batch_f64(const fk_kf_desc *desc, const double *F, const double *Q, const double *H, const double *R_inv,
+                      const double *B, const double *u, const double *z, const uint8_t *mask,
+                      double *x, double *P_inv, double *means, double *covs, double *means_p, double *covs_p,
+                      int32_t *status, void *stream);
+
+/* InformationFilter.predict (information_filter.py:245-289) on a resident batch: one step, x / P_inv [N][n*n] in place.
+ * u [N][nu] (NULL when nu == 0).  desc->T is ignored (treated as 1); the rest of desc as for fk_info_batch_f64. */
+int fk_info_predict_f64(const fk_kf_desc *desc, const double *F, const double *Q, const double *B, const double *u,
+                        double *x, double *P_inv, int32_t *status, void *stream);
+
+/* InformationFilter.update (information_filter.py:178-243) on a resident batch: one step, x / P_inv in place; z [N][m],
+ * mask [N] (or NULL), R_inv the matrix to use (the reference's R_inv argument or its attribute).  y [N][m], K [N][n*m]: the
+ * residual and the gain of the tracks that update, or NULL (K is formed only when asked for).  desc->T is ignored. */
+int fk_info_update_f64(const fk_kf_desc *desc, const double *H, const double *R_inv, const double *z, const uint8_t *mask,
+                       double *x, double *P_inv, double *y, double *K, int32_t *status, void *stream);
+
 /* ------------------------------------------------------------------ */
 /* Unscented transform path                                           */
 /* ------------------------------------------------------------------ */
