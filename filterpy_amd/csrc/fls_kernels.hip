@@ -18,38 +18,16 @@
 #if defined(FK_FLS_GENERAL) && FK_FLS_GENERAL
 #define FK_ROLLED 1
 #endif
-#include "fk_device.hpp"
+#include "fk_bank.hpp"
 #include "fk_fls.hpp"
 
 namespace fk {
 
-// B u of one step (x = F x + B u, fixed_lag_smoother.py:270-272): B [n][nu] shared, u the lane's record of step t
-template <int NX, int LAYOUT>
-__device__ __forceinline__ void fls_control(const FlsArgs &a, const Lane &lr, long t, double (&bu)[NX])
-{
-    FK_UNROLL for (int r = 0; r < NX; ++r) bu[r] = 0.0;
-    if (a.nu <= 0) return;
-    const RecView<LAYOUT> uv(a.u + t * a.N * a.nu, lr, a.nu);
-    for (int j = 0; j < a.nu; ++j) {
-        const double uj = uv.load(j);
-        FK_UNROLL for (int r = 0; r < NX; ++r) {
-            if (r < a.n) {
-                const double b = a.B[r * a.nu + j];
-                bu[r] = (j == 0) ? b * uj : fma(b, uj, bu[r]);
-            }
-        }
-    }
-}
-
+// the model is F | Q | H | R as given, B u of step t (x = F x + B u, fixed_lag_smoother.py:270-272) is bank_control (fk_bank.hpp)
 template <int NX, int NZ>
 __device__ __forceinline__ void fls_fill_model(double *s_model, const FlsArgs &a)
 {
-    using SM = LdsModel<NX, NZ>;
-    lds_fill<NX, NX>(s_model + SM::OFF_F, a.F, a.n, a.n, 1.0, threadIdx.x);
-    lds_fill<NX, NX>(s_model + SM::OFF_Q, a.Q, a.n, a.n, 0.0, threadIdx.x);
-    lds_fill<NZ, NX>(s_model + SM::OFF_H, a.H, a.m, a.n, 0.0, threadIdx.x);
-    lds_fill<NZ, NZ>(s_model + SM::OFF_R, a.R, a.m, a.m, 1.0, threadIdx.x);
-    __syncthreads();
+    bank_fill_model<NX, NZ>(s_model, a.F, a.Q, a.H, a.R, a.n, a.m);
 }
 
 #if !(defined(FK_FLS_GENERAL) && FK_FLS_GENERAL)
@@ -87,7 +65,7 @@ fls_fast_kernel(const FlsArgs a)
         const long k = k0 + t;
         double z[NZ], bu[NX];
         load_rec<NZ, 1, LAYOUT, true>(z, a.z + t * N * NZ, ln, NZ, 1, 0.0);
-        fls_control<NX, LAYOUT>(a, ln, t, bu);
+        bank_control<NX, LAYOUT>(a, ln, a.u, t, bu);
         st |= fls_step<NX, NZ, LMAX>(x, P, z, sm, bu, a.nu > 0, a.rj_diag != 0, k, lag, pend, y, S);
         store_rec<NX, 1, LAYOUT, true>(x, a.xhat + t * N * NX, ln, NX, 1);
         const long j = k - Lf + 1;               // final now
@@ -126,10 +104,8 @@ fls_fast_kernel(const FlsArgs a)
 
 int FK_CAT(launch_fls_fast_, FK_NX, FK_NZ, FK_LMAX)(const FlsArgs &a, int layout, hipStream_t stream)
 {
-    const dim3 grid((unsigned)((a.N + BLOCK - 1) / BLOCK)), block(BLOCK);
-    if (layout == LAYOUT_SOA) hipLaunchKernelGGL((fls_fast_kernel<FK_NX, FK_NZ, FK_LMAX, LAYOUT_SOA>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((fls_fast_kernel<FK_NX, FK_NZ, FK_LMAX, LAYOUT_AOS>), grid, block, 0, stream, a);
-    return check_launch("fls_fast_kernel");
+    return bank_launch(fls_fast_kernel<FK_NX, FK_NZ, FK_LMAX, LAYOUT_SOA>, fls_fast_kernel<FK_NX, FK_NZ, FK_LMAX, LAYOUT_AOS>,
+                       "fls_fast_kernel", a, layout, stream);
 }
 
 #else  // FK_FLS_GENERAL
@@ -171,7 +147,7 @@ fls_general_kernel(const FlsArgs a)
         const long k = a.k0 + t;
         double z[GZ], bu[GX], xpre[GX], w[GX], G[GX * GX];
         load_rec<GZ, 1, LAYOUT, false>(z, a.z + t * N * m, ln, m, 1, 0.0);
-        fls_control<GX, LAYOUT>(a, ln, t, bu);
+        bank_control<GX, LAYOUT>(a, ln, a.u, t, bu);
         st |= fls_filter_step<GX, GZ>(x, P, z, sm, bu, a.nu > 0, a.rj_diag != 0, xpre, w, G, y, S);
         store_rec<GX, 1, LAYOUT, false>(x, a.xhat + t * N * n, ln, n, 1);
         const bool smooth = k >= (long)lag;
@@ -200,10 +176,7 @@ fls_general_kernel(const FlsArgs a)
 
 int launch_fls_general(const FlsArgs &a, int layout, hipStream_t stream)
 {
-    const dim3 grid((unsigned)((a.N + BLOCK - 1) / BLOCK)), block(BLOCK);
-    if (layout == LAYOUT_SOA) hipLaunchKernelGGL((fls_general_kernel<LAYOUT_SOA>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((fls_general_kernel<LAYOUT_AOS>), grid, block, 0, stream, a);
-    return check_launch("fls_general_kernel");
+    return bank_launch(fls_general_kernel<LAYOUT_SOA>, fls_general_kernel<LAYOUT_AOS>, "fls_general_kernel", a, layout, stream);
 }
 
 #endif

@@ -17,7 +17,7 @@
 #if defined(FK_INFO_GENERAL) && FK_INFO_GENERAL
 #define FK_ROLLED 1
 #endif
-#include "fk_device.hpp"
+#include "fk_bank.hpp"
 #include "fk_info.hpp"
 
 namespace fk {
@@ -40,24 +40,6 @@ struct InfoLdsModel {
     __device__ __forceinline__ void rowHtRi(int i, double (&r)[NZ]) const { row<NZ>(OFF_HR + i * NZ, r); }
 };
 
-// B u of one step: B [n][nu] shared, u the lane's record (u_blk: the step's record block)
-template <int NX, int LAYOUT>
-__device__ __forceinline__ void info_control(const InfoArgs &a, const Lane &ln, const double *u_blk, double (&bu)[NX])
-{
-    FK_UNROLL for (int r = 0; r < NX; ++r) bu[r] = 0.0;
-    if (a.nu <= 0) return;
-    const RecView<LAYOUT> uv(u_blk, ln, a.nu);
-    for (int j = 0; j < a.nu; ++j) {
-        const double uj = uv.load(j);
-        FK_UNROLL for (int r = 0; r < NX; ++r) {
-            if (r < a.n) {
-                const double b = a.B[r * a.nu + j];
-                bu[r] = (j == 0) ? b * uj : fma(b, uj, bu[r]);
-            }
-        }
-    }
-}
-
 // F, Q, H as given (NULL in the phase that does not read them: pure padding); HtRi = H' R_inv, then G = HtRi H on the lower
 // triangle, mirrored.  Two barriers, both before any lane leaves.
 template <int NX, int NZ>
@@ -79,21 +61,6 @@ __device__ __forceinline__ void info_fill_model(double *s_model, const InfoArgs 
         s_model[SM::OFF_G + k] = (meas && hi < a.n) ? info_g_entry(s_model + SM::OFF_HR + hi * NZ, a.H, a.n, a.m, lo) : 0.0;
     }
     __syncthreads();
-}
-
-// One record per lane of the step's history block (block t of `base`, [N][E]).  WAVE (the fast kernel in NumPy order): the
-// wave's 64 records leave through an LDS transpose as contiguous 16-byte stores (wave_store_aos, fk_device.hpp; every lane of
-// the wave takes part -- tail lanes carry a copy of the last track and the descriptor drops their rows); otherwise lane stores.
-template <int R, int C, int LAYOUT, bool EXACT, bool WAVE>
-__device__ __forceinline__ void info_put(const double (&v)[R * C], double *base, long t, const Lane &ln, int r, int c,
-                                         double *tile, unsigned last_row)
-{
-    if constexpr (WAVE) {
-        const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-        wave_store_aos<R * C>(v, base + (t * ln.N + ln.blk0) * (R * C), wave * 64u, tile, lane, last_row);
-    } else {
-        store_rec<R, C, LAYOUT, EXACT>(v, base + t * ln.N * r * c, ln, r, c);
-    }
 }
 
 // The whole launch for one lane: NX, NZ the register shapes (the real n, m when EXACT).  last_row: the block's last real
@@ -124,11 +91,11 @@ __device__ __forceinline__ void info_lane(const InfoArgs &a, const double *s_mod
     for (long t = 0; t < a.T; ++t) {
         if (do_predict && !uf) {
             double bu[NX];
-            info_control<NX, LAYOUT>(a, ln, a.nu > 0 ? a.u + t * N * a.nu : nullptr, bu);
+            bank_control<NX, LAYOUT>(a, ln, a.nu > 0 ? a.u + t * N * a.nu : nullptr, 0, bu);
             st |= info_predict<NX>(x, Pi, P, have_P, sm, bu, a.nu > 0, n);
             have_P = false;
-            if (a.means_p) info_put<NX, 1, LAYOUT, EXACT, WAVE>(x, a.means_p, t, ln, n, 1, tile, last_row);
-            if (a.covs_p) info_put<NX, NX, LAYOUT, EXACT, WAVE>(Pi, a.covs_p, t, ln, n, n, tile, last_row);
+            if (a.means_p) bank_put<NX, 1, LAYOUT, EXACT, WAVE>(x, a.means_p, t, ln, n, 1, tile, last_row);
+            if (a.covs_p) bank_put<NX, NX, LAYOUT, EXACT, WAVE>(Pi, a.covs_p, t, ln, n, n, tile, last_row);
         }
         if (do_update) {
             const bool upd = a.mask == nullptr || a.mask[t * N + track] != 0;
@@ -141,16 +108,16 @@ __device__ __forceinline__ void info_lane(const InfoArgs &a, const double *s_mod
                 if (a.y) store_rec<NZ, 1, LAYOUT, EXACT>(y, a.y, ln, m, 1);
                 if (a.K) store_rec<NX, NZ, LAYOUT, EXACT>(K, a.K, ln, n, m);
             }
-            if (a.means) info_put<NX, 1, LAYOUT, EXACT, WAVE>(x, a.means, t, ln, n, 1, tile, last_row);
-            if (a.covs) info_put<NX, NX, LAYOUT, EXACT, WAVE>(Pi, a.covs, t, ln, n, n, tile, last_row);
+            if (a.means) bank_put<NX, 1, LAYOUT, EXACT, WAVE>(x, a.means, t, ln, n, 1, tile, last_row);
+            if (a.covs) bank_put<NX, NX, LAYOUT, EXACT, WAVE>(Pi, a.covs, t, ln, n, n, tile, last_row);
         }
         if (do_predict && uf) {
             double bu[NX];
-            info_control<NX, LAYOUT>(a, ln, a.nu > 0 ? a.u + t * N * a.nu : nullptr, bu);
+            bank_control<NX, LAYOUT>(a, ln, a.nu > 0 ? a.u + t * N * a.nu : nullptr, 0, bu);
             st |= info_predict<NX>(x, Pi, P, have_P, sm, bu, a.nu > 0, n);
             have_P = false;
-            if (a.means_p) info_put<NX, 1, LAYOUT, EXACT, WAVE>(x, a.means_p, t, ln, n, 1, tile, last_row);
-            if (a.covs_p) info_put<NX, NX, LAYOUT, EXACT, WAVE>(Pi, a.covs_p, t, ln, n, n, tile, last_row);
+            if (a.means_p) bank_put<NX, 1, LAYOUT, EXACT, WAVE>(x, a.means_p, t, ln, n, 1, tile, last_row);
+            if (a.covs_p) bank_put<NX, NX, LAYOUT, EXACT, WAVE>(Pi, a.covs_p, t, ln, n, n, tile, last_row);
         }
     }
     store_rec<NX, 1, LAYOUT, EXACT>(x, a.x, ln, n, 1);
@@ -183,10 +150,8 @@ info_fast_kernel(const InfoArgs a)
 
 int FK_CAT(launch_info_fast_, FK_NX, FK_NZ)(const InfoArgs &a, int layout, hipStream_t stream)
 {
-    const dim3 grid((unsigned)((a.N + BLOCK - 1) / BLOCK)), block(BLOCK);
-    if (layout == LAYOUT_SOA) hipLaunchKernelGGL((info_fast_kernel<FK_NX, FK_NZ, LAYOUT_SOA>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((info_fast_kernel<FK_NX, FK_NZ, LAYOUT_AOS>), grid, block, 0, stream, a);
-    return check_launch("info_fast_kernel");
+    return bank_launch(info_fast_kernel<FK_NX, FK_NZ, LAYOUT_SOA>, info_fast_kernel<FK_NX, FK_NZ, LAYOUT_AOS>,
+                       "info_fast_kernel", a, layout, stream);
 }
 
 #else  // FK_INFO_GENERAL
@@ -207,10 +172,7 @@ info_general_kernel(const InfoArgs a)
 
 int launch_info_general(const InfoArgs &a, int layout, hipStream_t stream)
 {
-    const dim3 grid((unsigned)((a.N + BLOCK - 1) / BLOCK)), block(BLOCK);
-    if (layout == LAYOUT_SOA) hipLaunchKernelGGL((info_general_kernel<LAYOUT_SOA>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((info_general_kernel<LAYOUT_AOS>), grid, block, 0, stream, a);
-    return check_launch("info_general_kernel");
+    return bank_launch(info_general_kernel<LAYOUT_SOA>, info_general_kernel<LAYOUT_AOS>, "info_general_kernel", a, layout, stream);
 }
 
 #endif

@@ -4,11 +4,7 @@
 //                         T steps in one launch)
 // fk_srkf_predict_f64  <- SquareRootKalmanFilter.predict           (square_root.py:226-248)
 // fk_srkf_update_f64   <- SquareRootKalmanFilter.update            (square_root.py:172-224)
-#include <hip/hip_runtime.h>
-#include <stdlib.h>
-
-#include "../../include/filterhip.h"
-#include "fk_device.hpp"
+#include "fk_dispatch.hpp"
 #include "fk_srkf.hpp"
 
 namespace fk {
@@ -18,57 +14,17 @@ namespace fk {
 #undef FK_SRKF_INST
 int launch_srkf_general(const SrkfArgs &, int, hipStream_t);
 
-struct SrkfEntry {
-    int nx, nz;
-    int (*fn)(const SrkfArgs &, int, hipStream_t);
-};
-static const SrkfEntry srkf_table[] = {
-#define FK_SRKF_INST(NX, NZ) {NX, NZ, launch_srkf_fast_##NX##_##NZ},
+static const FastEntry<SrkfArgs> srkf_table[] = {
+#define FK_SRKF_INST(NX, NZ) {NX, NZ, 0, launch_srkf_fast_##NX##_##NZ},
 #include "fk_dims_srkf.def"
 #undef FK_SRKF_INST
 };
 
-static int fail(int code, const char *msg)
-{
-    set_last_error(msg);
-    return code;
-}
-
-// The fast kernel serves exact (n, m); FK_SRKF_GENERAL=1 in the environment forces the general kernel (A/B and tests).  Nothing
-// else enters the choice: chained calls run the kernel one call would.
-static const SrkfEntry *pick_srkf(int n, int m)
-{
-    const char *ev = getenv("FK_SRKF_GENERAL");
-    if (ev && atoi(ev) != 0) return nullptr;
-    for (const SrkfEntry &e : srkf_table)
-        if (e.nx == n && e.nz == m) return &e;
-    return nullptr;
-}
-
-// Everything about desc that does not need a pointer; T is ignored for the single steps (treated as 1).
-static int check_desc(const fk_kf_desc *d, bool steps)
-{
-    if (!d) return fail(FK_ERR_BAD_ARG, "desc is NULL");
-    if (d->n < 1 || d->m < 1 || d->nu < 0) return fail(FK_ERR_BAD_ARG, "dim_x, dim_z must be >= 1, dim_u >= 0");
-    if (d->N < 0 || (steps && d->T < 0)) return fail(FK_ERR_BAD_ARG, "N and T must be >= 0");
-    if (d->layout != FK_LAYOUT_AOS && d->layout != FK_LAYOUT_SOA) return fail(FK_ERR_BAD_ARG, "bad layout");
-    if (d->n > 16 || d->m > 8) return fail(FK_ERR_UNSUPPORTED, "dim_x/dim_z outside the compiled range (dim_x <= 16, dim_z <= 8)");
-    if (d->model_mode != FK_MODEL_SHARED) return fail(FK_ERR_UNSUPPORTED, "square-root filter: FK_MODEL_SHARED only");
-    if (d->alpha_sq != 1.0 || d->flags != 0) return fail(FK_ERR_UNSUPPORTED, "square-root filter: alpha_sq 1 and flags 0 only");
-    return FK_OK;
-}
+static const Family SRKF{"square-root filter", /*update_first*/ true, /*flags*/ 0, /*k0*/ false};
 
 static int launch(const fk_kf_desc *d, SrkfArgs &a, void *stream)
 {
-    // one step's record block is addressed with 32-bit byte offsets (fk_device.hpp)
-    const long mx = d->n > d->m ? d->n : d->m;
-    long E = mx * mx;
-    if (d->nu > E) E = d->nu;
-    if ((double)d->N * (double)E * 8.0 >= 4294967264.0) return fail(FK_ERR_UNSUPPORTED, "N * dim^2 * 8 bytes must stay below 4 GiB (split the bank)");
-    a.N = d->N;
-    a.n = d->n; a.m = d->m; a.nu = d->nu;
-    const SrkfEntry *e = pick_srkf(d->n, d->m);
-    return e ? e->fn(a, d->layout, (hipStream_t)stream) : launch_srkf_general(a, d->layout, (hipStream_t)stream);
+    return launch_filter(d, a, stream, srkf_table, "FK_SRKF_GENERAL", launch_srkf_general);
 }
 
 }  // namespace fk
@@ -81,12 +37,12 @@ extern "C" int fk_srkf_batch_f64(const fk_kf_desc *desc, const double *F, const 
                                  double *sqrt_covs_p, double *y, double *K, double *S1_2, double *SI1_2,
                                  int32_t *status, void *stream)
 {
-    const int rc = check_desc(desc, true);
+    int rc = check_desc(desc, SRKF, true);
     if (rc != FK_OK) return rc;
     const fk_kf_desc *d = desc;
     if (d->N == 0 || d->T == 0) return FK_OK;                 // nothing to read, nothing to touch
     if (!F || !Q1_2 || !H || !R1_2 || !z || !x || !P1_2) return fail(FK_ERR_BAD_ARG, "F,Q1_2,H,R1_2,z,x,P1_2 must not be NULL");
-    if (d->nu > 0 && (!B || !u)) return fail(FK_ERR_BAD_ARG, "dim_u > 0 needs B and u");
+    if ((rc = check_control(d, B, u)) != FK_OK) return rc;
     SrkfArgs a{};
     a.F = F; a.Q12 = Q1_2; a.H = H; a.R12 = R1_2; a.B = d->nu > 0 ? B : nullptr; a.u = d->nu > 0 ? u : nullptr; a.z = z;
     a.mask = mask; a.x = x; a.P12 = P1_2;
@@ -99,12 +55,12 @@ extern "C" int fk_srkf_batch_f64(const fk_kf_desc *desc, const double *F, const 
 extern "C" int fk_srkf_predict_f64(const fk_kf_desc *desc, const double *F, const double *Q1_2, const double *B,
                                    const double *u, double *x, double *P1_2, int32_t *status, void *stream)
 {
-    const int rc = check_desc(desc, false);
+    int rc = check_desc(desc, SRKF, false);
     if (rc != FK_OK) return rc;
     const fk_kf_desc *d = desc;
     if (d->N == 0) return FK_OK;
     if (!F || !Q1_2 || !x || !P1_2) return fail(FK_ERR_BAD_ARG, "F,Q1_2,x,P1_2 must not be NULL");
-    if (d->nu > 0 && (!B || !u)) return fail(FK_ERR_BAD_ARG, "dim_u > 0 needs B and u");
+    if ((rc = check_control(d, B, u)) != FK_OK) return rc;
     SrkfArgs a{};
     a.F = F; a.Q12 = Q1_2; a.B = d->nu > 0 ? B : nullptr; a.u = d->nu > 0 ? u : nullptr;
     a.x = x; a.P12 = P1_2; a.status = status;
@@ -116,7 +72,7 @@ extern "C" int fk_srkf_update_f64(const fk_kf_desc *desc, const double *H, const
                                   const uint8_t *mask, double *x, double *P1_2, double *y, double *K, double *S1_2,
                                   double *SI1_2, int32_t *status, void *stream)
 {
-    const int rc = check_desc(desc, false);
+    int rc = check_desc(desc, SRKF, false);
     if (rc != FK_OK) return rc;
     const fk_kf_desc *d = desc;
     if (d->N == 0) return FK_OK;

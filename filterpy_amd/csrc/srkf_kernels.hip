@@ -16,39 +16,10 @@
 #if defined(FK_SRKF_GENERAL) && FK_SRKF_GENERAL
 #define FK_ROLLED 1
 #endif
-#include "fk_device.hpp"
+#include "fk_bank.hpp"
 #include "fk_srkf.hpp"
 
 namespace fk {
-
-// B u of one step: B [n][nu] shared, u the lane's record (u_blk: the step's record block)
-template <int NX, int LAYOUT>
-__device__ __forceinline__ void srkf_control(const SrkfArgs &a, const Lane &ln, const double *u_blk, double (&bu)[NX])
-{
-    FK_UNROLL for (int r = 0; r < NX; ++r) bu[r] = 0.0;
-    if (a.nu <= 0) return;
-    const RecView<LAYOUT> uv(u_blk, ln, a.nu);
-    for (int j = 0; j < a.nu; ++j) {
-        const double uj = uv.load(j);
-        FK_UNROLL for (int r = 0; r < NX; ++r) {
-            if (r < a.n) {
-                const double b = a.B[r * a.nu + j];
-                bu[r] = (j == 0) ? b * uj : fma(b, uj, bu[r]);
-            }
-        }
-    }
-}
-
-template <int NX, int NZ>
-__device__ __forceinline__ void srkf_fill_model(double *s_model, const SrkfArgs &a)
-{
-    using SM = LdsModel<NX, NZ>;
-    lds_fill<NX, NX>(s_model + SM::OFF_F, a.F, a.n, a.n, 1.0, threadIdx.x);
-    lds_fill<NX, NX>(s_model + SM::OFF_Q, a.Q12, a.n, a.n, 0.0, threadIdx.x);
-    lds_fill<NZ, NX>(s_model + SM::OFF_H, a.H, a.m, a.n, 0.0, threadIdx.x);
-    lds_fill<NZ, NZ>(s_model + SM::OFF_R, a.R12, a.m, a.m, 1.0, threadIdx.x);
-    __syncthreads();
-}
 
 // the lower triangle of a loaded factor (its upper triangle is not read: zeros)
 template <int NX>
@@ -56,21 +27,6 @@ __device__ __forceinline__ void srkf_lower(double (&L)[NX * NX])
 {
     FK_UNROLL for (int r = 0; r < NX; ++r)
         FK_UNROLL for (int c = r + 1; c < NX; ++c) L[r * NX + c] = 0.0;
-}
-
-// One record per lane of the step's history block (block t of `base`, [N][E]).  WAVE (the fast kernel in NumPy order): the
-// wave's 64 records leave through an LDS transpose as contiguous 16-byte stores (wave_store_aos, fk_device.hpp; every lane of
-// the wave takes part -- tail lanes carry a copy of the last track and the descriptor drops their rows); otherwise lane stores.
-template <int R, int C, int LAYOUT, bool EXACT, bool WAVE>
-__device__ __forceinline__ void srkf_put(const double (&v)[R * C], double *base, long t, const Lane &ln, int r, int c,
-                                         double *tile, unsigned last_row)
-{
-    if constexpr (WAVE) {
-        const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-        wave_store_aos<R * C>(v, base + (t * ln.N + ln.blk0) * (R * C), wave * 64u, tile, lane, last_row);
-    } else {
-        store_rec<R, C, LAYOUT, EXACT>(v, base + t * ln.N * r * c, ln, r, c);
-    }
 }
 
 // The whole launch for one lane: NX, NZ the register shapes (the real n, m when EXACT).  last_row: the block's last real
@@ -96,10 +52,10 @@ __device__ __forceinline__ void srkf_lane(const SrkfArgs &a, const double *s_mod
     for (long t = 0; t < a.T; ++t) {
         if (do_predict && !uf) {
             double bu[NX];
-            srkf_control<NX, LAYOUT>(a, ln, a.nu > 0 ? a.u + t * N * a.nu : nullptr, bu);
+            bank_control<NX, LAYOUT>(a, ln, a.nu > 0 ? a.u + t * N * a.nu : nullptr, 0, bu);
             srkf_predict<NX>(x, L, sm, bu, a.nu > 0);
-            if (a.means_p) srkf_put<NX, 1, LAYOUT, EXACT, WAVE>(x, a.means_p, t, ln, n, 1, tile, last_row);
-            if (a.covs_p) srkf_put<NX, NX, LAYOUT, EXACT, WAVE>(L, a.covs_p, t, ln, n, n, tile, last_row);
+            if (a.means_p) bank_put<NX, 1, LAYOUT, EXACT, WAVE>(x, a.means_p, t, ln, n, 1, tile, last_row);
+            if (a.covs_p) bank_put<NX, NX, LAYOUT, EXACT, WAVE>(L, a.covs_p, t, ln, n, n, tile, last_row);
         }
         if (do_update) {
             const bool upd = a.mask == nullptr || a.mask[t * N + track] != 0;
@@ -113,15 +69,15 @@ __device__ __forceinline__ void srkf_lane(const SrkfArgs &a, const double *s_mod
                 if (a.S12) store_rec<NZ, NZ, LAYOUT, EXACT>(S, a.S12, ln, m, m);
                 if (a.SI12) store_rec<NZ, NZ, LAYOUT, EXACT>(SI, a.SI12, ln, m, m);
             }
-            if (a.means) srkf_put<NX, 1, LAYOUT, EXACT, WAVE>(x, a.means, t, ln, n, 1, tile, last_row);
-            if (a.covs) srkf_put<NX, NX, LAYOUT, EXACT, WAVE>(L, a.covs, t, ln, n, n, tile, last_row);
+            if (a.means) bank_put<NX, 1, LAYOUT, EXACT, WAVE>(x, a.means, t, ln, n, 1, tile, last_row);
+            if (a.covs) bank_put<NX, NX, LAYOUT, EXACT, WAVE>(L, a.covs, t, ln, n, n, tile, last_row);
         }
         if (do_predict && uf) {
             double bu[NX];
-            srkf_control<NX, LAYOUT>(a, ln, a.nu > 0 ? a.u + t * N * a.nu : nullptr, bu);
+            bank_control<NX, LAYOUT>(a, ln, a.nu > 0 ? a.u + t * N * a.nu : nullptr, 0, bu);
             srkf_predict<NX>(x, L, sm, bu, a.nu > 0);
-            if (a.means_p) srkf_put<NX, 1, LAYOUT, EXACT, WAVE>(x, a.means_p, t, ln, n, 1, tile, last_row);
-            if (a.covs_p) srkf_put<NX, NX, LAYOUT, EXACT, WAVE>(L, a.covs_p, t, ln, n, n, tile, last_row);
+            if (a.means_p) bank_put<NX, 1, LAYOUT, EXACT, WAVE>(x, a.means_p, t, ln, n, 1, tile, last_row);
+            if (a.covs_p) bank_put<NX, NX, LAYOUT, EXACT, WAVE>(L, a.covs_p, t, ln, n, n, tile, last_row);
         }
     }
     store_rec<NX, 1, LAYOUT, EXACT>(x, a.x, ln, n, 1);
@@ -142,7 +98,8 @@ srkf_fast_kernel(const SrkfArgs a)
     constexpr int TILE = 64 * ((NX * NX) | 1);    // wave_store_aos's tile: 64 records of the longest history, odd row stride
     __shared__ double s_model[LdsModel<NX, NZ>::SIZE];
     __shared__ double s_tile[WAVE ? (BLOCK / 64) * TILE : 1];
-    srkf_fill_model<NX, NZ>(s_model, a);          // (the only barrier: lanes past N may leave after it unless WAVE)
+    // (the only barrier: lanes past N may leave after it unless WAVE)
+    bank_fill_model<NX, NZ>(s_model, a.F, a.Q12, a.H, a.R12, a.n, a.m);
     const long left = a.N - (long)blockIdx.x * BLOCK;
     const unsigned last_row = (unsigned)(left < BLOCK ? left : BLOCK) - 1u;
     if (!WAVE && threadIdx.x > last_row) return;
@@ -154,10 +111,8 @@ srkf_fast_kernel(const SrkfArgs a)
 
 int FK_CAT(launch_srkf_fast_, FK_NX, FK_NZ)(const SrkfArgs &a, int layout, hipStream_t stream)
 {
-    const dim3 grid((unsigned)((a.N + BLOCK - 1) / BLOCK)), block(BLOCK);
-    if (layout == LAYOUT_SOA) hipLaunchKernelGGL((srkf_fast_kernel<FK_NX, FK_NZ, LAYOUT_SOA>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((srkf_fast_kernel<FK_NX, FK_NZ, LAYOUT_AOS>), grid, block, 0, stream, a);
-    return check_launch("srkf_fast_kernel");
+    return bank_launch(srkf_fast_kernel<FK_NX, FK_NZ, LAYOUT_SOA>, srkf_fast_kernel<FK_NX, FK_NZ, LAYOUT_AOS>,
+                       "srkf_fast_kernel", a, layout, stream);
 }
 
 #else  // FK_SRKF_GENERAL
@@ -169,7 +124,7 @@ __global__ void __launch_bounds__(BLOCK)
 srkf_general_kernel(const SrkfArgs a)
 {
     __shared__ double s_model[LdsModel<GX, GZ>::SIZE];
-    srkf_fill_model<GX, GZ>(s_model, a);
+    bank_fill_model<GX, GZ>(s_model, a.F, a.Q12, a.H, a.R12, a.n, a.m);
     const long left = a.N - (long)blockIdx.x * BLOCK;
     const unsigned last_row = (unsigned)(left < BLOCK ? left : BLOCK) - 1u;
     if (threadIdx.x > last_row) return;
@@ -178,10 +133,7 @@ srkf_general_kernel(const SrkfArgs a)
 
 int launch_srkf_general(const SrkfArgs &a, int layout, hipStream_t stream)
 {
-    const dim3 grid((unsigned)((a.N + BLOCK - 1) / BLOCK)), block(BLOCK);
-    if (layout == LAYOUT_SOA) hipLaunchKernelGGL((srkf_general_kernel<LAYOUT_SOA>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((srkf_general_kernel<LAYOUT_AOS>), grid, block, 0, stream, a);
-    return check_launch("srkf_general_kernel");
+    return bank_launch(srkf_general_kernel<LAYOUT_SOA>, srkf_general_kernel<LAYOUT_AOS>, "srkf_general_kernel", a, layout, stream);
 }
 
 #endif

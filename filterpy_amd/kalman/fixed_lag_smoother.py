@@ -28,7 +28,8 @@ Shapes the reference broadcasts into nonsense raise ValueError instead:
 import numpy as np
 
 from .. import _engine as E
-from .._abi import FK_MODEL_SHARED, FK_KF_FLAG_R_JOSEPH_DIAG
+from .._abi import FK_KF_FLAG_R_JOSEPH_DIAG
+from ._bank import _bank_controls, _check_u_orientation, _control, _desc, _device_zs, _host_zs, _xshape, _z
 from .kalman_filter import _mat
 
 __all__ = ["FixedLagSmoother", "FixedLagSmootherBank"]
@@ -55,26 +56,6 @@ def _model(F, Q, H, R, n, m):
     return Fm, Qm, Hm, Rm, flags
 
 
-def _control(B, n, us_shape_tail, what="u"):
-    """B attribute + the shape of one step's u -> (B (n, nu) matrix, nu), or (None, 0) for no control input"""
-    size = int(np.prod(us_shape_tail)) if len(us_shape_tail) else 1
-    if np.isscalar(B) or np.ndim(B) == 0:
-        b = float(B)
-        if size != n:
-            raise ValueError(f"with a scalar B, {what} must have dim_x = {n} entries (b u = (b I) u), got shape {tuple(us_shape_tail)}")
-        if b == 0.0:
-            return None, 0
-        return np.eye(n) * b, n
-    Bm = np.asarray(B, dtype=np.float64)
-    if Bm.ndim == 1 and n == 1:
-        Bm = Bm.reshape(1, -1)
-    if Bm.ndim != 2 or Bm.shape[0] != n:
-        raise ValueError(f"B has shape {Bm.shape}, expected ({n}, dim_u)")
-    if size != Bm.shape[1]:
-        raise ValueError(f"{what} has {size} entries, B has {Bm.shape[1]} columns")
-    return np.ascontiguousarray(Bm), Bm.shape[1]
-
-
 def _run(n, m, N, layout, lag, k0, x, P, z, F, Q, H, R, rflags, B=None, u=None, pend=None, want_yS=False):
     """One fk_fls_batch_f64 launch.  x (N, n), P (N, n, n) host arrays or device records; z (T, N, m) host or device records;
     u (T, N, nu) or None; pend: device records of the W = min(max(lag, 1) - 1, k0) pending rows (W, N, n), or None when W = 0.
@@ -95,9 +76,8 @@ def _run(n, m, N, layout, lag, k0, x, P, z, F, Q, H, R, rflags, B=None, u=None, 
     nu = 0 if B is None else int(B.shape[1])
     dB = E.dev(B) if nu else None
     du = rec(u, 1) if nu else None
-    desc = dict(n=n, m=m, nu=nu, model_mode=FK_MODEL_SHARED, N=N, T=T, layout=E.LAYOUTS[layout],
-                update_first=0, alpha_sq=1.0, flags=rflags)
-    E.fls_batch(desc, lag, k0, E.dev(F), E.dev(Q), E.dev(H), E.dev(R), dz, dx, dP, xs, xhat, B=dB, u=du, y=y, S=S, status=st)
+    E.fls_batch(_desc(n, m, nu, N, T, layout, flags=rflags), lag, k0, E.dev(F), E.dev(Q), E.dev(H), E.dev(R), dz, dx, dP, xs, xhat,
+                B=dB, u=du, y=y, S=S, status=st)
     E.raise_on_status(st, "fixed-lag smoother")
     return xs, xhat, dx, dP, y, S
 
@@ -126,33 +106,11 @@ class FixedLagSmoother(object):
             self.xSmooth = []
 
     # -- shapes -------------------------------------------------------------------------------------------------------------
-    def _xshape(self):
-        n = self.dim_x
-        x = np.asarray(self.x, dtype=np.float64)
-        if x.shape not in ((n,), (n, 1)):
-            raise ValueError(f"x has shape {x.shape}, expected ({n},) or ({n}, 1)")
-        return x.shape
-
-    def _z(self, z, xshape):
-        """one step's measurement -> (m,) row, refusing the shapes the reference turns into nonsense"""
-        m = self.dim_z
-        za = np.asarray(z, dtype=np.float64)
-        column = len(xshape) == 2
-        if za.ndim == 0 and m == 1:
-            ok = True
-        elif column:
-            ok = za.shape == (m, 1) or (m == 1 and za.shape == (1,))
-        else:
-            ok = za.shape == (m,)
-        if not ok:
-            raise ValueError(f"measurement of shape {za.shape} with x of shape {xshape}: expected "
-                             + (f"({m}, 1)" if column else f"({m},)") + (" or a scalar" if m == 1 else ""))
-        return za.reshape(m)
-
     def _zs(self, zs, xshape):
-        return np.stack([self._z(z, xshape) for z in zs]) if len(zs) else np.zeros((0, self.dim_z))
+        m = self.dim_z
+        return np.stack([_z(z, m, xshape).reshape(m) for z in zs]) if len(zs) else np.zeros((0, self.dim_z))
 
-    def _controls(self, us, T, xshape=None):
+    def _us(self, us, T, xshape=None):
         """us (T steps) -> (B (n, nu), u (T, nu)) or (None, None); each u in x's orientation (xshape)"""
         if us is None:
             return None, None
@@ -165,12 +123,7 @@ class FixedLagSmoother(object):
             raise ValueError("every control input must have the same shape")
         B, nu = _control(self.B, self.dim_x, ua[0].shape if ua else (self.dim_x,))
         if ua and xshape is not None:
-            # x_pre += dot(B, u) (or b u): u must keep x's orientation, else x_pre becomes an (n, n) matrix / numpy refuses
-            sh, n = ua[0].shape, self.dim_x
-            ok = sh == (nu, 1) or (n == 1 and sh == (nu,)) if len(xshape) == 2 else sh == (nu,)
-            if not ok:
-                raise ValueError(f"control input of shape {sh} with x of shape {xshape}: expected "
-                                 + (f"({nu}, 1)" if len(xshape) == 2 else f"({nu},)"))
+            _check_u_orientation(ua[0].shape, nu, self.dim_x, xshape)
         if B is None:
             return None, None
         return B, np.stack([u.reshape(nu) for u in ua])
@@ -184,14 +137,14 @@ class FixedLagSmoother(object):
         """fixed_lag_smoother.py:217-311: (xSmooth, xhat) of shape (T, dim_x) for a 1-D x, (T, dim_x, 1) for a column x.
         One launch; the object's x and P are left alone."""
         n, m = self.dim_x, self.dim_z
-        xshape = self._xshape()
+        xshape = _xshape(self.x, n)
         zs = list(zs) if not isinstance(zs, np.ndarray) else zs
         T = len(zs)
         out_shape = (T,) + xshape
         if T == 0:
             return np.zeros(out_shape), np.zeros(out_shape)
         z = self._zs(zs, xshape)
-        B, u = self._controls(us, T, xshape)
+        B, u = self._us(us, T, xshape)
         F, Q, H, R, rflags = _model(self.F, self.Q, self.H, self.R, n, m)
         x, P = self._state()
         xs, xhat, *_ = _run(n, m, 1, "aos", _lag(N), 0, x, P, z.reshape(T, 1, m), F, Q, H, R, rflags,
@@ -204,9 +157,9 @@ class FixedLagSmoother(object):
         xSmooth = self.xSmooth                       # AttributeError without N, like the reference
         n, m = self.dim_x, self.dim_z
         lag, k = _lag(self.N), self.count
-        xshape = self._xshape()
-        zr = self._z(z, xshape)
-        B, uu = (None, None) if u is None else self._controls([u], 1, xshape)
+        xshape = _xshape(self.x, n)
+        zr = _z(z, m, xshape)
+        B, uu = (None, None) if u is None else self._us([u], 1, xshape)
         F, Q, H, R, rflags = _model(self.F, self.Q, self.H, self.R, n, m)
         x, P = self._state()
         W = min(max(lag, 1) - 1, k)
@@ -319,31 +272,12 @@ class FixedLagSmootherBank(object):
         return x.reshape(N, n), np.ascontiguousarray(P)
 
     def _inputs(self, zs, us, T):
+        """zs and us as _run takes them: device records or (T, N, m) host measurements (no missing rows here), B and u on
+        the host"""
         import torch
         n, m, N = self.dim_x, self.dim_z, self.n_tracks
-        if isinstance(zs, torch.Tensor):
-            want = (T, N, m) if self.layout == "aos" else (T, m, N)
-            if tuple(zs.shape) != want:
-                raise ValueError(f"device zs has shape {tuple(zs.shape)}, expected {want} ({self.layout} records)")
-            z = zs.to(dtype=torch.float64).contiguous()
-        else:
-            z = np.asarray(zs, dtype=np.float64)
-            if z.shape != (T, N, m) and not (m == 1 and z.shape == (T, N)):
-                raise ValueError(f"zs has shape {z.shape}, expected ({T}, {N}, {m})")
-            z = z.reshape(T, N, m)
-        B = u = None
-        if us is not None:
-            ua = np.asarray(us, dtype=np.float64)
-            if ua.ndim == 2:
-                ua = ua[:, :, None]
-            if ua.ndim != 3 or ua.shape[:2] != (T, N):
-                raise ValueError(f"us has shape {ua.shape}, expected ({T}, {N}, dim_u)")
-            if self.B is None:
-                raise ValueError("us given but B is None")
-            B, nu = _control(self.B, n, ua.shape[2:], "us")
-            if B is not None:
-                u = np.ascontiguousarray(ua)
-        return z, B, u
+        z = _device_zs(zs, T, N, m, self.layout) if isinstance(zs, torch.Tensor) else _host_zs(zs, T, N, m)
+        return (z,) + _bank_controls(self.B, us, T, N, n)
 
     def smooth_batch(self, zs, N, us=None, device_outputs=False):
         """(xSmooth, xhat), each (T, n_tracks, dim_x), for the whole run in one launch.  x and P are left alone."""

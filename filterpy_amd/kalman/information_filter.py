@@ -37,9 +37,8 @@ import numpy as np
 
 from .. import _engine as E
 from ..common.helpers import logpdf
-from .fixed_lag_smoother import _control
+from ._bank import _SharedModelBank, _desc, _step_control, _xshape, _z
 from .kalman_filter import _mat
-from .square_root import _desc, _step_control
 
 __all__ = ["InformationFilter", "InformationFilterBank"]
 
@@ -93,30 +92,6 @@ class InformationFilter(object):
         self.x_post = np.copy(self.x)
         self.P_inv_post = np.copy(self.P_inv)
 
-    # -- shapes -------------------------------------------------------------------------------------------------------------
-    def _xshape(self):
-        n = self.dim_x
-        x = np.asarray(self.x, dtype=np.float64)
-        if x.shape not in ((n,), (n, 1)):
-            raise ValueError(f"x has shape {x.shape}, expected ({n},) or ({n}, 1)")
-        return x.shape
-
-    def _z(self, z, xshape):
-        """one measurement -> (m,) row, refusing the shapes the reference turns into nonsense"""
-        m = self.dim_z
-        za = np.asarray(z, dtype=np.float64)
-        column = len(xshape) == 2
-        if za.ndim == 0 and m == 1:
-            ok = True
-        elif column:
-            ok = za.shape == (m, 1) or (m == 1 and za.shape == (1,))
-        else:
-            ok = za.shape == (m,)
-        if not ok:
-            raise ValueError(f"measurement of shape {za.shape} with x of shape {xshape}: expected "
-                             + (f"({m}, 1)" if column else f"({m},)") + (" or a scalar" if m == 1 else ""))
-        return za
-
     def _check_inv(self):
         if self.inv is not np.linalg.inv:
             raise NotImplementedError("InformationFilter.inv other than numpy.linalg.inv: the inverses are taken on the device")
@@ -131,8 +106,8 @@ class InformationFilter(object):
             return
         self._check_inv()
         n, m = self.dim_x, self.dim_z
-        xshape = self._xshape()
-        za = self._z(z, xshape)
+        xshape = _xshape(self.x, n)
+        za = _z(z, m, xshape)
         Ri = _square(self.R_inv, m, "R_inv") if R_inv is None else _r_inv(R_inv, m)
         H = _mat(self.H, m, n, "H")
         Pi = _square(self.P_inv, n, "P_inv")
@@ -161,7 +136,7 @@ class InformationFilter(object):
         """information_filter.py:245-289, the invertible branch"""
         self._check_inv()
         n = self.dim_x
-        xshape = self._xshape()
+        xshape = _xshape(self.x, n)
         B, uu = _step_control(self.B, u, n, xshape)
         F = _mat(self._F, n, n, "F")
         Q = _square(self.Q, n, "Q")
@@ -231,7 +206,7 @@ class InformationFilter(object):
                            "K", "y", "z", "S", "B", "log_likelihood", "likelihood", "inv")])
 
 
-class InformationFilterBank(object):
+class InformationFilterBank(_SharedModelBank):
     """n_tracks independent information filters that share F, H, Q, R_inv and B, stepped in lock-step on the GPU:
 
         x (N, dim_x)   P_inv (N, dim_x, dim_x)   zs (T, N, dim_z)   us (T, N, dim_u)   B (dim_x, dim_u)
@@ -241,29 +216,23 @@ class InformationFilterBank(object):
     tensors in `layout` ('aos' [T][N][..], 'soa' [T][..][N]) -- from ONE launch; x and P_inv are left alone.  A singular P_inv
     (or F P F' + Q) raises numpy.linalg.LinAlgError."""
 
+    _ENGINE, _COV = "info", "P_inv"
+    _BYPRODUCTS = (("y", "y", "m"), ("K", "K", "nm"))
+    _SINGULAR = {"predict": " (P_inv or F P F' + Q is singular)", "update": " (P_inv + H' R_inv H is singular)",
+                 "batch_filter": " (P_inv or F P F' + Q is singular)"}
+
     def __init__(self, dim_x, dim_z, n_tracks, dim_u=0, layout="soa"):
-        if dim_x < 1 or dim_z < 1 or dim_u < 0 or n_tracks < 1:
-            raise ValueError("dim_x, dim_z, n_tracks must be >= 1 and dim_u >= 0")
-        if layout not in E.LAYOUTS:
-            raise ValueError("layout must be 'soa' or 'aos'")
-        self.dim_x, self.dim_z, self.dim_u, self.n_tracks, self.layout = dim_x, dim_z, dim_u, n_tracks, layout
-        self.x = np.zeros((n_tracks, dim_x))
+        super().__init__(dim_x, dim_z, n_tracks, dim_u, layout)
         self.P_inv = np.tile(np.eye(dim_x), (n_tracks, 1, 1))
         self.Q = np.eye(dim_x)
         self.R_inv = np.eye(dim_z)
-        self.F = np.eye(dim_x)
-        self.H = np.zeros((dim_z, dim_x))
-        self.B = None
-        # the last update's by-products per track (update() sets them for the tracks that update)
-        self.y = np.zeros((n_tracks, dim_z))
-        self.K = np.zeros((n_tracks, dim_x, dim_z))
 
     @property
     def P(self):
         """the covariances, inv(P_inv) per track (host)"""
         return np.linalg.inv(self._p_inv())
 
-    # -- plumbing -----------------------------------------------------------------------------------------------------------
+    # -- what the shared plumbing asks for ------------------------------------------------------------------------------------
     def _p_inv(self):
         n, N = self.dim_x, self.n_tracks
         Pi = np.asarray(self.P_inv, dtype=np.float64)
@@ -273,126 +242,22 @@ class InformationFilterBank(object):
             raise ValueError(f"P_inv has shape {Pi.shape}, expected ({N}, {n}, {n}) or ({n}, {n})")
         return np.ascontiguousarray(Pi)
 
-    def _model(self):
+    def _model(self, R_inv=None):
         n, m = self.dim_x, self.dim_z
-        return (E.dev(_mat(self.F, n, n, "F")), E.dev(_square(self.Q, n, "Q")), E.dev(_mat(self.H, m, n, "H")),
-                E.dev(_square(self.R_inv, m, "R_inv")))
+        model = (E.dev(_mat(self.F, n, n, "F")), E.dev(_square(self.Q, n, "Q")), E.dev(_mat(self.H, m, n, "H")),
+                 E.dev(_square(self.R_inv, m, "R_inv")))
+        if R_inv is not None:
+            model = model[:3] + (E.dev(_r_inv(R_inv, m)),)
+        return model
 
     def _state(self):
         n, N = self.dim_x, self.n_tracks
-        x = np.asarray(self.x, dtype=np.float64)
-        if x.size != N * n:
-            raise ValueError(f"x has shape {x.shape}, expected ({N}, {n})")
-        return (E.to_records(x.reshape(N, n), self.layout, 0).clone(),
-                E.to_records(self._p_inv().reshape(N, n * n), self.layout, 0).clone())
-
-    def _controls(self, us, T):
-        n, N = self.dim_x, self.n_tracks
-        if us is None:
-            return None, None
-        ua = np.asarray(us, dtype=np.float64)
-        if ua.ndim == 2:
-            ua = ua[:, :, None]
-        if ua.ndim != 3 or ua.shape[:2] != (T, N):
-            raise ValueError(f"us has shape {ua.shape}, expected ({T}, {N}, dim_u)")
-        if self.B is None:
-            raise ValueError("us given but B is None")
-        B, nu = _control(self.B, n, ua.shape[2:], "us")
-        if B is None:
-            return None, None
-        return E.dev(B), E.to_records(np.ascontiguousarray(ua), self.layout, 1)
-
-    def _measurements(self, zs, T, mask):
-        """zs (T, N, m) host (NaN rows missing) or device records -> (device z, device uint8 mask or None)"""
-        import torch
-        m, N = self.dim_z, self.n_tracks
-        if isinstance(zs, torch.Tensor):
-            want = (T, N, m) if self.layout == "aos" else (T, m, N)
-            if tuple(zs.shape) != want:
-                raise ValueError(f"device zs has shape {tuple(zs.shape)}, expected {want} ({self.layout} records)")
-            z = zs.to(dtype=torch.float64).contiguous()
-            keep = None
-        else:
-            za = np.asarray(zs, dtype=np.float64)
-            if za.shape != (T, N, m) and not (m == 1 and za.shape == (T, N)):
-                raise ValueError(f"zs has shape {za.shape}, expected ({T}, {N}, {m})")
-            za = za.reshape(T, N, m)
-            nan = np.isnan(za).any(axis=2)
-            keep = None if not nan.any() else ~nan
-            if keep is not None:
-                za = np.where(nan[:, :, None], 0.0, za)
-            z = E.to_records(za, self.layout, 1)
-        if mask is not None:
-            mk = np.asarray(mask, dtype=bool).reshape(T, N)
-            keep = mk if keep is None else (keep & mk)
-        dm = None if keep is None else torch.from_numpy(np.ascontiguousarray(keep, dtype=np.uint8)).to(E.require_gpu())
-        return z, dm
-
-    def _host(self, t, lead, rec_shape):
-        return E.host_records(t.cpu().numpy(), self.layout, lead, rec_shape)
-
-    # -- steps --------------------------------------------------------------------------------------------------------------
-    def predict(self, u=None):
-        """one predict for every track: u (n_tracks, dim_u) or None"""
-        import torch
-        n, N = self.dim_x, self.n_tracks
-        F, Q, _, _ = self._model()
-        B, du = self._controls(None if u is None else np.asarray(u, dtype=np.float64).reshape(1, N, -1), 1)
-        x, Pi = self._state()
-        st = torch.zeros(N, dtype=torch.int32, device=x.device)
-        nu = 0 if B is None else int(B.shape[1])
-        E.info_predict(_desc(n, self.dim_z, nu, N, 1, self.layout), F, Q, x, Pi, B=B,
-                       u=None if du is None else du.reshape(du.shape[1:]), status=st)
-        E.raise_on_status(st, "InformationFilterBank.predict (P_inv or F P F' + Q is singular)")
-        self.x = self._host(x, 0, (n,))
-        self.P_inv = self._host(Pi, 0, (n, n))
+        return self._x_records(), E.to_records(self._p_inv().reshape(N, n * n), self.layout, 0).clone()
 
     def update(self, z, R_inv=None, mask=None):
         """one update for every track: z (n_tracks, dim_z), NaN rows missing; R_inv a matrix or a scalar (eye * R_inv) for this
         call; mask (n_tracks,) bool, False = missing.  Sets y and K of the tracks that update."""
-        import torch
-        n, m, N = self.dim_x, self.dim_z, self.n_tracks
-        _, _, H, Ri = self._model()
-        if R_inv is not None:
-            Ri = E.dev(_r_inv(R_inv, m))
-        dz, dm = self._measurements(np.asarray(z, dtype=np.float64).reshape(1, N, m), 1,
-                                    None if mask is None else np.asarray(mask).reshape(1, N))
-        x, Pi = self._state()
-        outs = [E.to_records(np.asarray(getattr(self, k), dtype=np.float64).reshape(N, -1), self.layout, 0).clone()
-                for k in ("y", "K")]
-        st = torch.zeros(N, dtype=torch.int32, device=x.device)
-        E.info_update(_desc(n, m, 0, N, 1, self.layout), H, Ri, dz.reshape(dz.shape[1:]), x, Pi,
-                      mask=None if dm is None else dm.reshape(N), y=outs[0], K=outs[1], status=st)
-        E.raise_on_status(st, "InformationFilterBank.update (P_inv + H' R_inv H is singular)")
-        self.x = self._host(x, 0, (n,))
-        self.P_inv = self._host(Pi, 0, (n, n))
-        self.y, self.K = self._host(outs[0], 0, (m,)), self._host(outs[1], 0, (n, m))
-
-    def batch_filter(self, zs, mask=None, us=None, update_first=False, device_outputs=False):
-        """(means, P_invs, means_p, P_invs_p) of the whole run, ONE launch; x and P_inv are left alone.  zs (T, N, dim_z) with
-        NaN rows missing (or device records in `layout`), mask (T, N) bool (False = missing), us (T, N, dim_u)."""
-        import torch
-        n, m, N = self.dim_x, self.dim_z, self.n_tracks
-        T = int(zs.shape[0]) if hasattr(zs, "shape") else len(zs)
-        if T == 0:
-            e = np.zeros((0, N, n))
-            return e, np.zeros((0, N, n, n)), e.copy(), np.zeros((0, N, n, n))
-        F, Q, H, Ri = self._model()
-        dz, dm = self._measurements(zs, T, mask)
-        B, du = self._controls(us, T)
-        x, Pi = self._state()
-        dev = x.device
-        means, means_p = E.alloc_records((T,), N, n, self.layout, dev), E.alloc_records((T,), N, n, self.layout, dev)
-        covs, covs_p = E.alloc_records((T,), N, n * n, self.layout, dev), E.alloc_records((T,), N, n * n, self.layout, dev)
-        st = torch.zeros(N, dtype=torch.int32, device=dev)
-        nu = 0 if B is None else int(B.shape[1])
-        E.info_batch(_desc(n, m, nu, N, T, self.layout, update_first), F, Q, H, Ri, dz, x, Pi, B=B, u=du, mask=dm,
-                     means=means, covs=covs, means_p=means_p, covs_p=covs_p, status=st)
-        E.raise_on_status(st, "InformationFilterBank.batch_filter (P_inv or F P F' + Q is singular)")
-        if device_outputs:
-            return means, covs, means_p, covs_p
-        return (self._host(means, 1, (n,)), self._host(covs, 1, (n, n)),
-                self._host(means_p, 1, (n,)), self._host(covs_p, 1, (n, n)))
+        self._update(z, R_inv, mask)
 
     def __repr__(self):
         return "\n".join(["InformationFilterBank object (filterpy_amd, gfx950)"] +

@@ -29,8 +29,7 @@ from copy import deepcopy
 import numpy as np
 
 from .. import _engine as E
-from .._abi import FK_MODEL_SHARED
-from .fixed_lag_smoother import _control
+from ._bank import _SharedModelBank, _desc, _step_control, _xshape, _z
 from .kalman_filter import _mat
 
 __all__ = ["SquareRootKalmanFilter", "SquareRootKalmanFilterBank"]
@@ -50,34 +49,6 @@ def _factor(L, k, name):
     if np.any(np.triu(A, 1) != 0):
         raise ValueError(f"{name} must be a lower-triangular factor (the kernels do not read its upper triangle)")
     return np.ascontiguousarray(A)
-
-
-def _step_control(B, u, n, xshape):
-    """predict's x = F x + dot(B, u) -> (B (n, nu), u (nu,)) or (None, None)"""
-    if u is None:
-        return None, None
-    if np.ndim(u) == 0:
-        if float(u) == 0.0:
-            return None, None
-        if not (np.isscalar(B) or np.ndim(B) == 0):
-            raise ValueError("a nonzero scalar u with a matrix B: dot(B, u) would be an (n, dim_u) matrix")
-        b = float(B)
-        return (None, None) if b == 0.0 else (np.full((n, 1), b), np.array([float(u)]))
-    ua = np.asarray(u, dtype=np.float64)
-    Bm, nu = _control(B, n, ua.shape)
-    sh = ua.shape
-    ok = sh == (nu, 1) or (n == 1 and sh == (nu,)) if len(xshape) == 2 else sh == (nu,)
-    if not ok:
-        raise ValueError(f"control input of shape {sh} with x of shape {xshape}: expected "
-                         + (f"({nu}, 1)" if len(xshape) == 2 else f"({nu},)"))
-    if Bm is None:
-        return None, None
-    return Bm, ua.reshape(nu)
-
-
-def _desc(n, m, nu, N, T, layout, update_first=False):
-    return dict(n=n, m=m, nu=nu, model_mode=FK_MODEL_SHARED, N=N, T=T, layout=E.LAYOUTS[layout],
-                update_first=int(bool(update_first)), alpha_sq=1.0, flags=0)
 
 
 class SquareRootKalmanFilter(object):
@@ -115,30 +86,6 @@ class SquareRootKalmanFilter(object):
         self.x_post = np.copy(self.x)
         self._P1_2_post = np.copy(self._P1_2)
 
-    # -- shapes -------------------------------------------------------------------------------------------------------------
-    def _xshape(self):
-        n = self.dim_x
-        x = np.asarray(self.x, dtype=np.float64)
-        if x.shape not in ((n,), (n, 1)):
-            raise ValueError(f"x has shape {x.shape}, expected ({n},) or ({n}, 1)")
-        return x.shape
-
-    def _z(self, z, xshape):
-        """one measurement -> (m,) row, refusing the shapes the reference turns into nonsense"""
-        m = self.dim_z
-        za = np.asarray(z, dtype=np.float64)
-        column = len(xshape) == 2
-        if za.ndim == 0 and m == 1:
-            ok = True
-        elif column:
-            ok = za.shape == (m, 1) or (m == 1 and za.shape == (1,))
-        else:
-            ok = za.shape == (m,)
-        if not ok:
-            raise ValueError(f"measurement of shape {za.shape} with x of shape {xshape}: expected "
-                             + (f"({m}, 1)" if column else f"({m},)") + (" or a scalar" if m == 1 else ""))
-        return za.reshape(m)
-
     # -- the reference's methods --------------------------------------------------------------------------------------------
     def update(self, z, R2=None):
         """square_root.py:172-224.  z None: bookkeeping only (:189-193)."""
@@ -148,8 +95,8 @@ class SquareRootKalmanFilter(object):
             self._P1_2_post = np.copy(self._P1_2)
             return
         n, m = self.dim_x, self.dim_z
-        xshape = self._xshape()
-        zr = self._z(z, xshape)
+        xshape = _xshape(self.x, n)
+        zr = _z(z, m, xshape)
         if R2 is None:
             R2 = self._R1_2
         elif np.isscalar(R2):
@@ -184,7 +131,7 @@ class SquareRootKalmanFilter(object):
     def predict(self, u=0):
         """square_root.py:226-248"""
         n = self.dim_x
-        xshape = self._xshape()
+        xshape = _xshape(self.x, n)
         B, uu = _step_control(self.B, u, n, xshape)
         F = _mat(self.F, n, n, "F")
         Q12 = _factor(self._Q1_2, n, "Q1_2")
@@ -282,7 +229,7 @@ class SquareRootKalmanFilter(object):
                           ("dim_x", "dim_z", "dim_u", "x", "P", "F", "Q", "R", "H", "K", "y", "S", "SI", "M", "B")])
 
 
-class SquareRootKalmanFilterBank(object):
+class SquareRootKalmanFilterBank(_SharedModelBank):
     """n_tracks independent square-root filters that share F, H, Q, R and B, stepped in lock-step on the GPU:
 
         x (N, dim_x)   P1_2 (N, dim_x, dim_x)   zs (T, N, dim_z)   us (T, N, dim_u)   B (dim_x, dim_u)
@@ -293,24 +240,15 @@ class SquareRootKalmanFilterBank(object):
     with device_outputs=True the device tensors in `layout` ('aos' [T][N][..], 'soa' [T][..][N]) -- from ONE launch; x and P1_2
     are left alone."""
 
+    _ENGINE, _COV = "srkf", "_P1_2"
+    _BYPRODUCTS = (("y", "y", "m"), ("K", "K", "nm"), ("S1_2", "S12", "mm"), ("SI1_2", "SI12", "mm"))
+    _SINGULAR = {"update": " (S1_2 is singular)", "batch_filter": " (S1_2 is singular)"}
+
     def __init__(self, dim_x, dim_z, n_tracks, dim_u=0, layout="soa"):
-        if dim_x < 1 or dim_z < 1 or dim_u < 0 or n_tracks < 1:
-            raise ValueError("dim_x, dim_z, n_tracks must be >= 1 and dim_u >= 0")
-        if layout not in E.LAYOUTS:
-            raise ValueError("layout must be 'soa' or 'aos'")
-        self.dim_x, self.dim_z, self.dim_u, self.n_tracks, self.layout = dim_x, dim_z, dim_u, n_tracks, layout
-        self.x = np.zeros((n_tracks, dim_x))
+        super().__init__(dim_x, dim_z, n_tracks, dim_u, layout)
         self._P1_2 = np.tile(np.eye(dim_x), (n_tracks, 1, 1))
         self._Q1_2 = np.eye(dim_x)
         self._R1_2 = np.eye(dim_z)
-        self.F = np.eye(dim_x)
-        self.H = np.zeros((dim_z, dim_x))
-        self.B = None
-        # the last update's by-products per track (update() sets them for the tracks that update)
-        self.y = np.zeros((n_tracks, dim_z))
-        self.K = np.zeros((n_tracks, dim_x, dim_z))
-        self.S1_2 = np.zeros((n_tracks, dim_z, dim_z))
-        self.SI1_2 = np.zeros((n_tracks, dim_z, dim_z))
 
     @property
     def P(self):
@@ -362,133 +300,29 @@ class SquareRootKalmanFilterBank(object):
     def R1_2(self):
         return self._R1_2
 
-    # -- plumbing -----------------------------------------------------------------------------------------------------------
-    def _model(self):
+    # -- what the shared plumbing asks for ------------------------------------------------------------------------------------
+    def _model(self, R2=None):
         n, m = self.dim_x, self.dim_z
-        return (E.dev(_mat(self.F, n, n, "F")), E.dev(_factor(self._Q1_2, n, "Q1_2")), E.dev(_mat(self.H, m, n, "H")),
-                E.dev(_factor(self._R1_2, m, "R1_2")))
+        model = (E.dev(_mat(self.F, n, n, "F")), E.dev(_factor(self._Q1_2, n, "Q1_2")), E.dev(_mat(self.H, m, n, "H")),
+                 E.dev(_factor(self._R1_2, m, "R1_2")))
+        if R2 is not None:
+            model = model[:3] + (E.dev(_factor(np.eye(m) * R2 if np.isscalar(R2) else R2, m, "R2")),)
+        return model
 
     def _state(self):
         n, N = self.dim_x, self.n_tracks
-        x = np.asarray(self.x, dtype=np.float64)
-        if x.size != N * n:
-            raise ValueError(f"x has shape {x.shape}, expected ({N}, {n})")
+        x = self._x_records()
         L = np.asarray(self._P1_2, dtype=np.float64)
         if L.shape != (N, n, n):
             raise ValueError(f"P1_2 has shape {L.shape}, expected ({N}, {n}, {n})")
         if np.any(np.triu(L, 1) != 0):
             raise ValueError("P1_2 must be lower triangular")
-        return (E.to_records(x.reshape(N, n), self.layout, 0).clone(),
-                E.to_records(L.reshape(N, n * n), self.layout, 0).clone())
-
-    def _controls(self, us, T):
-        n, N = self.dim_x, self.n_tracks
-        if us is None:
-            return None, None
-        ua = np.asarray(us, dtype=np.float64)
-        if ua.ndim == 2:
-            ua = ua[:, :, None]
-        if ua.ndim != 3 or ua.shape[:2] != (T, N):
-            raise ValueError(f"us has shape {ua.shape}, expected ({T}, {N}, dim_u)")
-        if self.B is None:
-            raise ValueError("us given but B is None")
-        B, nu = _control(self.B, n, ua.shape[2:], "us")
-        if B is None:
-            return None, None
-        return E.dev(B), E.to_records(np.ascontiguousarray(ua), self.layout, 1)
-
-    def _measurements(self, zs, T, mask):
-        """zs (T, N, m) host (NaN rows missing) or device records -> (device z, device uint8 mask or None)"""
-        import torch
-        n, m, N = self.dim_x, self.dim_z, self.n_tracks
-        if isinstance(zs, torch.Tensor):
-            want = (T, N, m) if self.layout == "aos" else (T, m, N)
-            if tuple(zs.shape) != want:
-                raise ValueError(f"device zs has shape {tuple(zs.shape)}, expected {want} ({self.layout} records)")
-            z = zs.to(dtype=torch.float64).contiguous()
-            keep = None
-        else:
-            za = np.asarray(zs, dtype=np.float64)
-            if za.shape != (T, N, m) and not (m == 1 and za.shape == (T, N)):
-                raise ValueError(f"zs has shape {za.shape}, expected ({T}, {N}, {m})")
-            za = za.reshape(T, N, m)
-            nan = np.isnan(za).any(axis=2)
-            keep = None if not nan.any() else ~nan
-            if keep is not None:
-                za = np.where(nan[:, :, None], 0.0, za)
-            z = E.to_records(za, self.layout, 1)
-        if mask is not None:
-            mk = np.asarray(mask, dtype=bool).reshape(T, N)
-            keep = mk if keep is None else (keep & mk)
-        dm = None if keep is None else torch.from_numpy(np.ascontiguousarray(keep, dtype=np.uint8)).to(E.require_gpu())
-        return z, dm
-
-    def _host(self, t, lead, rec_shape):
-        return E.host_records(t.cpu().numpy(), self.layout, lead, rec_shape)
-
-    # -- steps --------------------------------------------------------------------------------------------------------------
-    def predict(self, u=None):
-        """one predict for every track: u (n_tracks, dim_u) or None"""
-        import torch
-        n, N = self.dim_x, self.n_tracks
-        F, Q12, _, _ = self._model()
-        B, du = self._controls(None if u is None else np.asarray(u, dtype=np.float64).reshape(1, N, -1), 1)
-        x, P12 = self._state()
-        st = torch.zeros(N, dtype=torch.int32, device=x.device)
-        nu = 0 if B is None else int(B.shape[1])
-        E.srkf_predict(_desc(n, self.dim_z, nu, N, 1, self.layout), F, Q12, x, P12, B=B,
-                       u=None if du is None else du.reshape(du.shape[1:]), status=st)
-        E.raise_on_status(st, "SquareRootKalmanFilterBank.predict")
-        self.x = self._host(x, 0, (n,))
-        self._P1_2 = self._host(P12, 0, (n, n))
+        return x, E.to_records(L.reshape(N, n * n), self.layout, 0).clone()
 
     def update(self, z, R2=None, mask=None):
         """one update for every track: z (n_tracks, dim_z), NaN rows missing; R2 a lower-triangular factor or a scalar
         (eye * R2) for this call; mask (n_tracks,) bool, False = missing.  Sets y, K, S1_2, SI1_2 of the tracks that update."""
-        import torch
-        n, m, N = self.dim_x, self.dim_z, self.n_tracks
-        _, _, H, R12 = self._model()
-        if R2 is not None:
-            R12 = E.dev(_factor(np.eye(m) * R2 if np.isscalar(R2) else R2, m, "R2"))
-        dz, dm = self._measurements(np.asarray(z, dtype=np.float64).reshape(1, N, m), 1,
-                                    None if mask is None else np.asarray(mask).reshape(1, N))
-        x, P12 = self._state()
-        shapes = ((m,), (n, m), (m, m), (m, m))
-        outs = [E.to_records(np.asarray(getattr(self, k), dtype=np.float64).reshape(N, -1), self.layout, 0).clone()
-                for k in ("y", "K", "S1_2", "SI1_2")]
-        st = torch.zeros(N, dtype=torch.int32, device=x.device)
-        E.srkf_update(_desc(n, m, 0, N, 1, self.layout), H, R12, dz.reshape(dz.shape[1:]), x, P12,
-                      mask=None if dm is None else dm.reshape(N), y=outs[0], K=outs[1], S12=outs[2], SI12=outs[3], status=st)
-        E.raise_on_status(st, "SquareRootKalmanFilterBank.update (S1_2 is singular)")
-        self.x = self._host(x, 0, (n,))
-        self._P1_2 = self._host(P12, 0, (n, n))
-        self.y, self.K, self.S1_2, self.SI1_2 = (self._host(o, 0, shp) for o, shp in zip(outs, shapes))
-
-    def batch_filter(self, zs, mask=None, us=None, update_first=False, device_outputs=False):
-        """(means, sqrt_covs, means_p, sqrt_covs_p) of the whole run, ONE launch; x and P1_2 are left alone.  zs (T, N, dim_z)
-        with NaN rows missing (or device records in `layout`), mask (T, N) bool (False = missing), us (T, N, dim_u)."""
-        import torch
-        n, m, N = self.dim_x, self.dim_z, self.n_tracks
-        T = int(zs.shape[0]) if hasattr(zs, "shape") else len(zs)
-        if T == 0:
-            e = np.zeros((0, N, n))
-            return e, np.zeros((0, N, n, n)), e.copy(), np.zeros((0, N, n, n))
-        F, Q12, H, R12 = self._model()
-        dz, dm = self._measurements(zs, T, mask)
-        B, du = self._controls(us, T)
-        x, P12 = self._state()
-        dev = x.device
-        means, means_p = E.alloc_records((T,), N, n, self.layout, dev), E.alloc_records((T,), N, n, self.layout, dev)
-        covs, covs_p = E.alloc_records((T,), N, n * n, self.layout, dev), E.alloc_records((T,), N, n * n, self.layout, dev)
-        st = torch.zeros(N, dtype=torch.int32, device=dev)
-        nu = 0 if B is None else int(B.shape[1])
-        E.srkf_batch(_desc(n, m, nu, N, T, self.layout, update_first), F, Q12, H, R12, dz, x, P12, B=B, u=du, mask=dm,
-                     means=means, covs=covs, means_p=means_p, covs_p=covs_p, status=st)
-        E.raise_on_status(st, "SquareRootKalmanFilterBank.batch_filter (S1_2 is singular)")
-        if device_outputs:
-            return means, covs, means_p, covs_p
-        return (self._host(means, 1, (n,)), self._host(covs, 1, (n, n)),
-                self._host(means_p, 1, (n,)), self._host(covs_p, 1, (n, n)))
+        self._update(z, R2, mask)
 
     def __repr__(self):
         return "\n".join(["SquareRootKalmanFilterBank object (filterpy_amd, gfx950)"] +

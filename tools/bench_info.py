@@ -82,6 +82,8 @@ def main():
     from filterpy_amd import _engine as E
     from filterpy_amd import _abi
     from filterpy_amd._abi import FK_MODEL_SHARED
+    if os.environ.get("FK_LIB"):      # an experimental build of the library (A/B of two builds in one lease); tools only
+        _abi.LIB_PATH = os.path.abspath(os.environ["FK_LIB"])
     fast = fast_table()
     torch.cuda.set_device(0)
     T = a.steps
