@@ -1,7 +1,10 @@
-// fk_dispatch.hpp -- what the C-ABI entry points of the shared-model banks have in common on the host (srkf_dispatch.cpp,
-// info_dispatch.cpp, fls_dispatch.cpp): the refusals every family makes before it touches a pointer, the table of exact-shape
-// kernels with its environment override, and the limit that 32-bit record offsets put on a bank.  Every message is part of
-// the ABI's behaviour (tests/test_host_refusals.py pins them).
+// fk_dispatch.hpp -- the host scaffold of every *_dispatch.cpp: what the C-ABI entry points have in common before a kernel
+// is chosen.  For all of them: fail, the B / u rule, the limit that 32-bit record offsets put on a bank, and the convention by
+// which a launcher hands a call on (NOT_SERVED) with the lookup over an instantiation table.  For the shared-model banks
+// (srkf_dispatch.cpp, info_dispatch.cpp, fls_dispatch.cpp) also the descriptor refusals by family and the table of exact-shape
+// kernels with its environment override; the Kalman filter and the IMM estimator (kf_dispatch.cpp, imm_dispatch.cpp) keep
+// their own descriptor rules and messages.  Every message is part of the ABI's behaviour (tests/test_host_refusals.py pins
+// them).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -17,6 +20,20 @@ inline int fail(int code, const char *msg)
 {
     set_last_error(msg);
     return code;
+}
+
+// A launcher answers FK_OK or an error once it has launched, and NOT_SERVED -- before it touches anything -- where the call is
+// not one its kernels carry (a model mode, an output set, a by-product): the dispatcher then tries its next candidate.
+constexpr int NOT_SERVED = 1;
+
+// The entry of an instantiation table ({nx, nz, ..., fn}; a table over dim_x alone holds nz = 0) made for exactly (nx, nz), or
+// nullptr.
+template <class Entry, size_t K>
+const Entry *find_entry(const Entry (&table)[K], int nx, int nz = 0)
+{
+    for (const Entry &e : table)
+        if (e.nx == nx && e.nz == nz) return &e;
+    return nullptr;
 }
 
 // One fast kernel: exact (nx, nz), and for the fixed-lag smoother lags up to lmax (0 where the family has no third dimension).
@@ -85,13 +102,20 @@ inline int check_control(const fk_kf_desc *d, const double *B, const double *u)
     return FK_OK;
 }
 
-// One step's record block is addressed with 32-bit byte offsets (fk_device.hpp).  E: the family's widest record in doubles
-// (the control record counts too).
+// One step's record block is addressed with 32-bit byte offsets (fk_device.hpp): `records` records of E doubles each must stay
+// below `limit` bytes.  Limit and words are the caller's: the Kalman filter and IMM entry points spell theirs differently.
+constexpr double FK_4GIB = 4294967296.0;
+inline int check_record_block(double records, double E, double limit, const char *msg)
+{
+    if (records * E * 8.0 >= limit) return fail(FK_ERR_UNSUPPORTED, msg);
+    return FK_OK;
+}
+
+// ... for the shared-model banks.  E: the family's widest record in doubles (the control record counts too).
 inline int check_record_block(const fk_kf_desc *d, long E)
 {
     if (d->nu > E) E = d->nu;
-    if ((double)d->N * (double)E * 8.0 >= 4294967264.0) return fail(FK_ERR_UNSUPPORTED, "N * dim^2 * 8 bytes must stay below 4 GiB (split the bank)");
-    return FK_OK;
+    return check_record_block((double)d->N, (double)E, FK_4GIB - 32.0, "N * dim^2 * 8 bytes must stay below 4 GiB (split the bank)");
 }
 
 // The launch of a predict / update filter (Args: N, n, m, nu): the fast kernel serves exact (n, m), the general kernel the
