@@ -238,6 +238,34 @@ def info_update(desc_kw, H, Rinv, z, x, Pinv, *, mask=None, y=None, K=None, stat
     _abi.check(rc, "fk_info_update_f64")
 
 
+ENKF_CHUNK = 2048         # members per workgroup and per slab of partial sums (csrc/fk_enkf.hpp: ENKF_CHUNK)
+
+
+def enkf_workspace_bytes(n, m, N):
+    return int(_abi.lib().fk_enkf_workspace_bytes(n, m, N))
+
+
+def enkf_predict(desc_kw, noise, sigmas, x, P, workspace, *, F=None, factor=None, workspace_bytes=None, status=None):
+    """fk_enkf_predict_f64: F s + e for every member, the new mean and covariance (include/filterhip.h).  workspace: a uint8
+    tensor of enkf_workspace_bytes(n, m, N) bytes; workspace_bytes defaults to its size."""
+    d = fk_kf_desc(**desc_kw)
+    nbytes = workspace.numel() * workspace.element_size() if workspace_bytes is None else int(workspace_bytes)
+    rc = _abi.lib().fk_enkf_predict_f64(d, _ptr(F), _ptr(noise), _ptr(factor), _ptr(sigmas), _ptr(x), _ptr(P), _ptr(workspace),
+                                        nbytes, _ptr(status), _stream())
+    _abi.check(rc, "fk_enkf_predict_f64")
+
+
+def enkf_update(desc_kw, R, z, noise, sigmas, x, P, workspace, *, H=None, sigmas_h=None, factor=None, S=None, SI=None, K=None,
+                workspace_bytes=None, status=None):
+    """fk_enkf_update_f64: the ensemble update with h = H s formed in-lane (H) or read (sigmas_h); include/filterhip.h"""
+    d = fk_kf_desc(**desc_kw)
+    nbytes = workspace.numel() * workspace.element_size() if workspace_bytes is None else int(workspace_bytes)
+    rc = _abi.lib().fk_enkf_update_f64(d, _ptr(H), _ptr(sigmas_h), _ptr(R), _ptr(z), _ptr(noise), _ptr(factor), _ptr(sigmas),
+                                       _ptr(x), _ptr(P), _ptr(S), _ptr(SI), _ptr(K), _ptr(workspace), nbytes, _ptr(status),
+                                       _stream())
+    _abi.check(rc, "fk_enkf_update_f64")
+
+
 def ut_sigma_points(n, N, layout, scale, x, P, sigmas, status=None):
     rc = _abi.lib().fk_ut_sigma_points_f64(n, N, LAYOUTS[layout], float(scale), _ptr(x), _ptr(P),
                                            _ptr(sigmas), _ptr(status), _stream())

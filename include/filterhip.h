@@ -303,6 +303,34 @@ int fk_info_predict_f64(const fk_kf_desc *desc, const double *F, const double *Q
 int fk_info_update_f64(const fk_kf_desc *desc, const double *H, const double *R_inv, const double *z, const uint8_t *mask,
                        double *x, double *P_inv, double *y, double *K, int32_t *status, void *stream);
 
+/* EnsembleKalmanFilter (filterpy/kalman/ensemble_kalman_filter.py:218-290): ONE filter whose state is an ensemble of N members,
+ * sigmas [N][n] in `layout`.  The parallelism is over the members; the means and covariances are reductions over all of them,
+ * summed in a fixed order (per workgroup of 2048 members, then over the workgroups in index order by a second launch): the
+ * same call gives the same bytes.  The random draws are INPUTS: noise [N][d] records in `layout` (d = n for predict, m for
+ * update) hold either the draws themselves (factor NULL) or standard normals w with e = factor' w, factor [d*d] row-major
+ * (numpy.random.multivariate_normal's own factor sqrt(s)[:, None] * v of the SVD of the covariance, so e = w @ factor).
+ *   desc      : n (1..16), m (1..8), N (>= 2: the ensemble size), layout; model_mode FK_MODEL_SHARED, alpha_sq 1, flags 0,
+ *               nu >= 0 (unused); T and update_first are ignored.
+ *   workspace : fk_enkf_workspace_bytes(n, m, N) bytes of device memory, 8-byte aligned; contents need not survive between
+ *               calls.  A smaller workspace_bytes is FK_ERR_WORKSPACE.
+ *   status    : one int32 (or NULL): FK_STATUS_NOT_PD (update: a pivot of the L D L' of S at or below m eps max|diag S|),
+ *               FK_STATUS_NONFINITE.
+ * Each call is a short chain of launches on `stream` (predict two, update four).
+ *
+ * predict (:275-290):  s_i <- F s_i (F [n*n]; NULL: s_i stays), s_i += e_i;  x = mean(s);  P = sum (s - x)(s - x)' / (N - 1).
+ *   x [n]: in: a value near the ensemble's mean (the previous x), the pivot of the one-pass sums -- the result depends on it
+ *   in rounding only; out: the new mean.  P [n*n] out.  F NULL with a factor serves initialize() (members preset to x).
+ * update (:218-273):  h_i = H s_i (H [m*n]) or h_i read from sigmas_h [N][m] records (exactly one of the two is given);
+ *   z_mean = mean(h);  S = sum (h - z_mean)(h - z_mean)' / (N - 1) + R;  P_xz = sum (s - x)(h - z_mean)' / (N - 1) with the x
+ *   given (the reference centres the members on self.x as it stands);  SI = S^-1;  K = P_xz SI;  s_i += K (z + e_i - h_i);
+ *   x = mean(s);  P -= K S K'.  R [m*m], z [m];  x [n] in/out, P [n*n] in/out;  S, SI [m*m], K [n*m] out (each may be NULL). */
+size_t fk_enkf_workspace_bytes(int32_t n, int32_t m, int64_t N);
+int fk_enkf_predict_f64(const fk_kf_desc *desc, const double *F, const double *noise, const double *factor, double *sigmas,
+                        double *x, double *P, void *workspace, size_t workspace_bytes, int32_t *status, void *stream);
+int fk_enkf_update_f64(const fk_kf_desc *desc, const double *H, const double *sigmas_h, const double *R, const double *z,
+                       const double *noise, const double *factor, double *sigmas, double *x, double *P, double *S, double *SI,
+                       double *K, void *workspace, size_t workspace_bytes, int32_t *status, void *stream);
+
 /* ------------------------------------------------------------------ */
 /* Unscented transform path                                           */
 /* ------------------------------------------------------------------ */
