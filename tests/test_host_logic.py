@@ -325,7 +325,7 @@ def test_counted_waits_behind_lds_dma_requests_have_their_stores():
     if not os.path.isdir(build):
         pytest.skip("library not built here (the objects do not travel with the .so)")
     objs = sorted(set(glob.glob(os.path.join(build, "inst_imm_2_1_*_p[1256].o")) + glob.glob(os.path.join(build, "inst_imm_4_2_*_p[1256].o"))
-                      + glob.glob(os.path.join(build, "inst_imm_6_3_*_p[1256].o")) + glob.glob(os.path.join(build, "inst_imm_9_4_[234]_*_p[1256].o"))
+                      + glob.glob(os.path.join(build, "inst_imm_6_3_*_p[1256].o"))
                       + glob.glob(os.path.join(build, "inst_fast_[789]_*.o")) + glob.glob(os.path.join(build, "inst_mlg_1[06]_*.o"))
                       + glob.glob(os.path.join(build, "ukf_mlg_1[06].o"))))
     assert len(objs) > 40, len(objs)
@@ -372,11 +372,12 @@ def test_no_specialised_instantiation_spills_under_a_launch_bound_of_its_own_mak
     assert not bad, bad
 
 
-def test_two_stage_build_lists_are_consistent():
-    """csrc/Makefile links the library twice in a cold build: stage 1 from every object except the slow unrolled IMM classes, with
-    rolled stand-ins (build/quick/) in their place -- a complete library half-way through --, stage 2 as shipped.  The lists
-    the two link lines are made of: every slow object has exactly one stand-in of the same name, no object is linked twice, and
-    the two link lines differ in nothing else."""
+def test_link_line_is_one_object_per_line_of_the_instantiation_lists():
+    """csrc/Makefile compiles every object and links the library once.  What the link line is made of (`OBJS`, read off make's
+    own database): no object twice, and for every FK_*_INST list of the fk_dims*.def files exactly one object per line, named
+    after the line's fields -- eight parts per line for the IMM classes --, plus the padded general kernel and the dispatcher of
+    the four bank families.  Nothing of the former two-stage build (stand-in objects, a stage stamp, side targets) is left."""
+    import re
     import subprocess
     csrc = os.path.join(ROOT, "filterpy_amd", "csrc")
     db = subprocess.run(["make", "-C", csrc, "-pnq"], capture_output=True, text=True).stdout
@@ -386,18 +387,36 @@ def test_two_stage_build_lists_are_consistent():
             if line.startswith(name + " := ") or line.startswith(name + " = "):
                 return line.split("=", 1)[1].split()
         raise AssertionError(name + " not in the Makefile's database")
-    base, slow, quick, objs = var("BASE_OBJS"), var("SLOW_OBJS"), var("QUICK_OBJS"), var("OBJS")
-    assert len(set(objs)) == len(objs) and set(objs) == set(base) | set(slow) and not set(base) & set(slow)
-    assert sorted(q.replace("build/quick/", "build/") for q in quick) == sorted(slow) and len(slow) % 8 == 0
-    # the slow classes are exactly the ones built with the general kernel only (all eight parts of each)
-    classes = sorted({o.rsplit("_p", 1)[0] for o in slow})
-    assert all(sum(o.startswith(c + "_p") for o in slow) == 8 for c in classes)
-    # where the shipped library and the stage stamp both exist, the library is stage 2's (stage 1 dates its own before the stamp)
-    lib, stamp = os.path.join(ROOT, "filterpy_amd", "libfilterhip.so"), os.path.join(csrc, "build", "stage1.stamp")
-    if os.path.exists(lib) and os.path.exists(stamp) and os.path.getmtime(lib) < os.path.getmtime(stamp):
-        import warnings
-        warnings.warn("filterpy_amd/libfilterhip.so is a STAGE 1 library (rolled stand-ins for the slow IMM classes): the build "
-                      "was cut short; `make -C filterpy_amd/csrc -j` finishes it")
+    objs = var("OBJS")
+    assert len(set(objs)) == len(objs)
+    # macro -> (list file, object prefix); the fields of a line joined by "_" are the rest of the name
+    lists = {"KF": ("fk_dims.def", "inst_kf"), "FAST": ("fk_dims_fast.def", "inst_fast"), "RTS": ("fk_dims_rts.def", "inst_rts"),
+             "MLG": ("fk_dims_mlg.def", "inst_mlg"), "RMLG": ("fk_dims_mlg.def", "inst_rmlg"), "RMLX": ("fk_dims_mlg.def", "inst_rmlx"),
+             "FLS": ("fk_dims_fls.def", "inst_fls"), "SRKF": ("fk_dims_srkf.def", "inst_srkf"), "INFO": ("fk_dims_info.def", "inst_info"),
+             "ENKF": ("fk_dims_enkf.def", "inst_enkf"), "IMM": ("fk_dims_imm.def", "inst_imm")}
+    macros = set()
+    for f in sorted(os.listdir(csrc)):
+        if f.startswith("fk_dims") and f.endswith(".def"):
+            macros |= {(f, m) for m in re.findall(r"^FK_(\w+)_INST\(", open(os.path.join(csrc, f)).read(), re.M)}
+    assert macros == {(f, m) for m, (f, _) in lists.items()}, macros          # a new list must be pinned here too
+    want = []
+    for macro, (f, prefix) in lists.items():
+        lines = re.findall(r"^FK_%s_INST\(([^)]*)\)" % macro, open(os.path.join(csrc, f)).read(), re.M)
+        assert lines, macro
+        names = ["_".join(x.strip() for x in l.split(",")) for l in lines]
+        parts = ["_p%d" % p for p in range(8)] if macro == "IMM" else [""]
+        want += ["build/%s_%s%s.o" % (prefix, n, p) for n in names for p in parts]
+        if macro in ("FLS", "SRKF", "INFO", "ENKF"):
+            for o in ("build/%s_general.o" % macro.lower(), "build/%s_dispatch.o" % macro.lower()):
+                assert objs.count(o) == 1, o
+    assert len(set(want)) == len(want), [o for o in want if want.count(o) > 1]          # (a line listed twice)
+    assert sorted(o for o in objs if o.startswith("build/inst_")) == sorted(want)
+    # the two-stage machinery: neither a variable nor a target of its names, no second object directory, no stamp
+    gone = ["BASE_OBJS", "SLOW_CLASSES", "SLOW_OBJS", "QUICK_OBJS", "EARLY_N", "EARLY", "IMM_UNROLL_9", "IMM_GENERAL_9", "IMM_UNROLL_16",
+            "IMM_BIG_BANKS", "unrolled", "imm_flags", "stage1", "early", "slow_rest"]
+    left = re.findall(r"^(%s)[ \t]*(?::=|\?=|::=|=|:)" % "|".join(gone), db, re.M)
+    assert not left, left
+    assert "stage1" not in db and "build/quick" not in db
 
 
 def test_every_entry_point_refuses_null_and_nonsense_without_touching_a_device():
