@@ -75,6 +75,12 @@ SIGNATURES = {
     "fk_info_batch_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 16),
     "fk_info_predict_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 8),
     "fk_info_update_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 10),
+    "fk_ckf_sigma_points_f64": (ctypes.c_int, [c_i32, c_i64, c_i32] + [c_vp] * 5),
+    "fk_ckf_transform_f64": (ctypes.c_int, [c_i32, c_i32, c_i64, c_i32] + [c_vp] * 5),
+    "fk_ckf_update_f64": (ctypes.c_int, [c_i32, c_i32, c_i64, c_i32] + [c_vp] * 14),
+    "fk_ckf_linear_batch_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 15),
+    "fk_ckf_linear_predict_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 7),
+    "fk_ckf_linear_update_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 13),
     "fk_enkf_workspace_bytes": (c_sz, [c_i32, c_i32, c_i64]),
     "fk_enkf_predict_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 7 + [c_sz, c_vp, c_vp]),
     "fk_enkf_update_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 13 + [c_sz, c_vp, c_vp]),

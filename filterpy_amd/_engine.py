@@ -238,6 +238,52 @@ def info_update(desc_kw, H, Rinv, z, x, Pinv, *, mask=None, y=None, K=None, stat
     _abi.check(rc, "fk_info_update_f64")
 
 
+def ckf_sigma_points(n, N, layout, x, P, sigmas, status=None):
+    """fk_ckf_sigma_points_f64: the 2n cubature points x +- sqrt(n) U[k] per track, sigmas [N][2n*n] (include/filterhip.h)"""
+    rc = _abi.lib().fk_ckf_sigma_points_f64(n, N, LAYOUTS[layout], _ptr(x), _ptr(P), _ptr(sigmas), _ptr(status), _stream())
+    _abi.check(rc, "fk_ckf_sigma_points_f64")
+
+
+def ckf_transform(d, k, N, layout, sigmas, noise, x_out, P_out):
+    """fk_ckf_transform_f64: mean and covariance (+ noise) of k cubature points of dimension d per track"""
+    rc = _abi.lib().fk_ckf_transform_f64(d, k, N, LAYOUTS[layout], _ptr(sigmas), _ptr(noise), _ptr(x_out), _ptr(P_out), _stream())
+    _abi.check(rc, "fk_ckf_transform_f64")
+
+
+def ckf_update(n, m, N, layout, sigmas_f, sigmas_h, R, z, x, P, *, zp=None, S=None, SI=None, Pxz=None, K=None, y=None,
+               status=None):
+    """fk_ckf_update_f64: the whole cubature update from both point sets in one launch; zp None: z already holds y"""
+    rc = _abi.lib().fk_ckf_update_f64(n, m, N, LAYOUTS[layout], _ptr(sigmas_f), _ptr(sigmas_h), _ptr(R), _ptr(z), _ptr(x), _ptr(P),
+                                      _ptr(zp), _ptr(S), _ptr(SI), _ptr(Pxz), _ptr(K), _ptr(y), _ptr(status), _stream())
+    _abi.check(rc, "fk_ckf_update_f64")
+
+
+def ckf_linear_batch(desc_kw, F, Q, H, R, z, x, P, points, *, mask=None, means=None, covs=None, means_p=None, covs_p=None,
+                     status=None):
+    """fk_ckf_linear_batch_f64: T steps of the cubature filter on a matrix model (x, P and the points record [N][n + n*n] in and
+    out; include/filterhip.h)."""
+    _keep = []
+    d = fk_kf_desc(**desc_kw)
+    rc = _abi.lib().fk_ckf_linear_batch_f64(d, _ptr(F), _ptr(Q), _ptr(H), _ptr(R), _ptr(z), _mask_ptr(mask, _keep), _ptr(x),
+                                            _ptr(P), _ptr(points), _ptr(means), _ptr(covs), _ptr(means_p), _ptr(covs_p),
+                                            _ptr(status), _stream())
+    _abi.check(rc, "fk_ckf_linear_batch_f64")
+
+
+def ckf_linear_predict(desc_kw, F, Q, x, P, points, *, status=None):
+    d = fk_kf_desc(**desc_kw)
+    rc = _abi.lib().fk_ckf_linear_predict_f64(d, _ptr(F), _ptr(Q), _ptr(x), _ptr(P), _ptr(points), _ptr(status), _stream())
+    _abi.check(rc, "fk_ckf_linear_predict_f64")
+
+
+def ckf_linear_update(desc_kw, H, R, z, x, P, points, *, mask=None, y=None, K=None, S=None, SI=None, status=None):
+    _keep = []
+    d = fk_kf_desc(**desc_kw)
+    rc = _abi.lib().fk_ckf_linear_update_f64(d, _ptr(H), _ptr(R), _ptr(z), _mask_ptr(mask, _keep), _ptr(x), _ptr(P), _ptr(points),
+                                             _ptr(y), _ptr(K), _ptr(S), _ptr(SI), _ptr(status), _stream())
+    _abi.check(rc, "fk_ckf_linear_update_f64")
+
+
 ENKF_CHUNK = 2048         # members per workgroup and per slab of partial sums (csrc/fk_enkf.hpp: ENKF_CHUNK)
 
 

@@ -303,6 +303,65 @@ int fk_info_predict_f64(const fk_kf_desc *desc, const double *F, const double *Q
 int fk_info_update_f64(const fk_kf_desc *desc, const double *H, const double *R_inv, const double *z, const uint8_t *mask,
                        double *x, double *P_inv, double *y, double *K, int32_t *status, void *stream);
 
+/* CubatureKalmanFilter (filterpy/kalman/CubatureKalmanFilter.py) for N independent filters.  2n cubature points and no centre
+ * point: x +- sqrt(n) U[k] with U = cholesky(P) upper (spherical_radial_sigmas, :32-61); mean and covariance of k points are
+ * x = sum / k, P = sum (X X' - x x') / k + noise (ckf_transform, :64-98); update() (:329-390) pushes the points predict() LEFT
+ * through hx -- it draws no new ones from the predicted P, so Q never reaches Pxz or S.
+ * The second moments are summed centred, sum (X - x)(X - x)', and P -= K S K' is formed as K Pxz' (K S = Pxz); P, S leave whole
+ * and exactly symmetric.  A pivot of cholesky(P) or of the L D L' of S that is not > 0 sets FK_STATUS_NOT_PD (the reference's
+ * cholesky raises).  P and R are symmetric: P's upper and R's lower triangle are read.
+ *
+ * The building blocks, for arbitrary fx / hx (n 1..16, m 1..8, records in `layout`):
+ *   fk_ckf_sigma_points_f64  x [N][n], P [N][n*n] -> sigmas [N][2n*n] (record = the (2n, n) C-order array), status [N] or NULL.
+ *   fk_ckf_transform_f64     sigmas [N][k*d] (k <= 32 points of dimension d <= 16), noise_cov [d*d] shared or NULL
+ *                            -> x_out [N][d], P_out [N][d*d].
+ *   fk_ckf_update_f64        :357-379 in ONE launch: sigmas_f [N][2n*n], sigmas_h [N][2n*m], R [m*m] shared, z [N][m];
+ *                            x [N][n], P [N][n*n] in place (Pxz is centred on x as it stands).  By-products, each may be NULL:
+ *                            zp [N][m], S, SI [N][m*m], Pxz, K [N][n*m], y [N][m].  zp == NULL also means that z already
+ *                            holds y = residual_z(z, zp) (a custom residual_z: the caller forms it from fk_ckf_transform_f64's
+ *                            mean of sigmas_h).  status [N] or NULL: FK_STATUS_NOT_PD (S), FK_STATUS_NONFINITE. */
+int fk_ckf_sigma_points_f64(int32_t n, int64_t N, int32_t layout, const double *x, const double *P, double *sigmas,
+                            int32_t *status, void *stream);
+int fk_ckf_transform_f64(int32_t d, int32_t k, int64_t N, int32_t layout, const double *sigmas, const double *noise_cov,
+                         double *x_out, double *P_out, void *stream);
+int fk_ckf_update_f64(int32_t n, int32_t m, int64_t N, int32_t layout, const double *sigmas_f, const double *sigmas_h,
+                      const double *R, const double *z, double *x, double *P, double *zp, double *S, double *SI, double *Pxz,
+                      double *K, double *y, int32_t *status, void *stream);
+
+/* The cubature filter on a matrix model, fx = F and hx = H shared by every track (predict :292-327, update :329-390), T steps
+ * of predict then update in ONE launch (the reference has no batch_filter, hence no update_first).  Point k of a +- pair is
+ * F x +- sqrt(n) F U[k]: the points predict leaves are held as the centre c = F x and the n half-differences E[k] = F U[k],
+ *   points [N][n + n*n]: c [n], then E [n][n] row by row;  sigmas_f[k] = c + sqrt(n) E[k], sigmas_f[n + k] = c - sqrt(n) E[k],
+ * and every sum over the 2n points is one over the n pairs:
+ *   predict  x = c;  P = sum_k E[k] E[k]' + Q
+ *   update   zp = H c;  G[k] = H E[k];  S = sum_k G[k] G[k]' + R;  Pxz = sum_k E[k] G[k]';  K = Pxz inv(S);  y = z - zp;
+ *            x += K y;  P -= K Pxz'
+ *   desc      : n (1..16), m (1..8), N, T, layout; model_mode FK_MODEL_SHARED, alpha_sq 1, flags 0, nu 0, update_first 0 --
+ *               anything else FK_ERR_UNSUPPORTED.
+ *   F [n*n], Q [n*n], H [m*n], R [m*m]: shared.   z [T][N][m]: records in `layout`.   mask: uint8 [T][N] (t-major), 0 = no
+ *               measurement (update(None), :348-352: x and P unchanged); NULL = every step updates.
+ *   x [N][n], P [N][n*n], points [N][n + n*n]: in: the state before the first step (points: what the last predict left; zeros
+ *               before any predict, as the reference's sigmas_f); out: after the last.
+ *   means, covs : posterior x / P per step [T][N][n] / [T][N][n*n]; means_p, covs_p: prior per step.  Each may be NULL.
+ *   status [N] or NULL: FK_STATUS_NOT_PD, FK_STATUS_NONFINITE.
+ * Which kernel runs depends on (n, m, layout) only, and the state is (x, P, points) alone: a run split into chained calls is
+ * bit-identical to one call. */
+int fk_ckf_linear_batch_f64(const fk_kf_desc *desc, const double *F, const double *Q, const double *H, const double *R,
+                            const double *z, const uint8_t *mask, double *x, double *P, double *points, double *means,
+                            double *covs, double *means_p, double *covs_p, int32_t *status, void *stream);
+
+/* CubatureKalmanFilter.predict with fx = F (:292-327) on a resident batch: one step, x / P in place, points written.
+ * desc->T is ignored (treated as 1); the rest of desc as for fk_ckf_linear_batch_f64. */
+int fk_ckf_linear_predict_f64(const fk_kf_desc *desc, const double *F, const double *Q, double *x, double *P, double *points,
+                              int32_t *status, void *stream);
+
+/* CubatureKalmanFilter.update with hx = H (:329-390) on a resident batch: one step on the points given, x / P in place;
+ * z [N][m], mask [N] (or NULL), R the matrix to use (the reference's R argument or its attribute).  y [N][m], K [N][n*m],
+ * S, SI [N][m*m]: by-products of the tracks that update, or NULL.  desc->T is ignored. */
+int fk_ckf_linear_update_f64(const fk_kf_desc *desc, const double *H, const double *R, const double *z, const uint8_t *mask,
+                             double *x, double *P, const double *points, double *y, double *K, double *S, double *SI,
+                             int32_t *status, void *stream);
+
 /* EnsembleKalmanFilter (filterpy/kalman/ensemble_kalman_filter.py:218-290): ONE filter whose state is an ensemble of N members,
  * sigmas [N][n] in `layout`.  The parallelism is over the members; the means and covariances are reductions over all of them,
  * summed in a fixed order (per workgroup of 2048 members, then over the workgroups in index order by a second launch): the
