@@ -2,9 +2,9 @@
 // is chosen.  For all of them: fail, the B / u rule, the limit that 32-bit record offsets put on a bank, and the convention by
 // which a launcher hands a call on (NOT_SERVED) with the lookup over an instantiation table.  For the shared-model banks
 // (srkf_dispatch.cpp, info_dispatch.cpp, fls_dispatch.cpp) also the descriptor refusals by family and the table of exact-shape
-// kernels with its environment override; the Kalman filter and the IMM estimator (kf_dispatch.cpp, imm_dispatch.cpp) keep
-// their own descriptor rules and messages.  Every message is part of the ABI's behaviour (tests/test_host_refusals.py pins
-// them).
+// kernels with its environment override; the Kalman filter with its variants, the IMM estimator and the unscented filter
+// (kf_dispatch.cpp, imm_dispatch.cpp, ukf_dispatch.cpp) keep their own rules and messages and take fail, find_entry and the
+// record-block guard.  Every message is part of the ABI's behaviour (tests/test_host_refusals.py pins them).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -5,9 +5,12 @@
 // fk_kf_predict_f64      <- KalmanFilter.predict       (:437-482)
 // fk_kf_update_f64       <- KalmanFilter.update        (:485-561)
 // fk_kf_rts_f64          <- KalmanFilter.rts_smoother  (:995-1074), module rts_smoother (:1792-1858)
+// fk_kf_steadystate_f64       <- KalmanFilter.predict_steadystate / update_steadystate (:563-668), T steps in one launch
+// fk_kf_update_correlated_f64 <- KalmanFilter.update_correlated (:670-752)
 #include "fk_dispatch.hpp"
 #include "fk_kernel_args.hpp"
 #include "fk_chunks.hpp"
+#include "fk_launchers.hpp"
 
 namespace fk {
 
@@ -475,6 +478,46 @@ int fk_kf_rts_f64(const fk_kf_desc *desc, const double *F, const double *Q, cons
         b.cnt = cnt;
         return route_rts(desc, b, general, (hipStream_t)stream);
     });
+}
+
+// The two variants (kf_variants.hip) keep rules and words of their own: sizes below 1 are FK_ERR_UNSUPPORTED, K / M is shared
+// or per track, the record block may reach 4 GiB exactly, and an empty bank is FK_OK only after the pointers are there.
+
+int fk_kf_steadystate_f64(const fk_kf_desc *d, const double *F, const double *H, const double *K, const double *B,
+                          const double *u, const double *z, const uint8_t *mask, double *x, double *means, double *means_p,
+                          double *y_out, void *stream)
+{
+    if (!d) return fail(FK_ERR_BAD_ARG, "desc is NULL");
+    if (d->n < 1 || d->n > 16 || d->m < 1 || d->m > 8 || d->nu < 0 || d->nu > 4)
+        return fail(FK_ERR_UNSUPPORTED, "steady state: dim_x 1..16, dim_z 1..8, dim_u 0..4");
+    if (d->layout != FK_LAYOUT_AOS && d->layout != FK_LAYOUT_SOA) return fail(FK_ERR_BAD_ARG, "steady state: bad layout");
+    if (d->model_mode != FK_MODEL_SHARED && d->model_mode != FK_MODEL_PER_TRACK)
+        return fail(FK_ERR_UNSUPPORTED, "steady state: K is shared or per track");
+    if (d->N < 0 || d->T < 0 || !x || (!F && !z) || (z && (!H || !K)) || (d->nu > 0 && F && (!B || !u)))
+        return fail(FK_ERR_BAD_ARG, "steady state: bad argument");
+    if (int rc = check_record_block((double)d->N, (double)d->n * d->m, FK_4GIB, "steady state: record block >= 4 GiB")) return rc;
+    if (d->N == 0 || d->T == 0) return FK_OK;
+    SteadyArgs a{};
+    a.F = F; a.H = H; a.K = K; a.B = (d->nu > 0 && F) ? B : nullptr; a.u = u; a.z = z; a.mask = mask;
+    a.x = x; a.means = means; a.means_p = means_p; a.y_out = y_out; a.N = d->N; a.T = d->T;
+    a.n = d->n; a.m = d->m; a.nu = d->nu; a.k_per_track = d->model_mode == FK_MODEL_PER_TRACK && K != nullptr;
+    return launch_steady(a, d->layout, (hipStream_t)stream);
+}
+
+int fk_kf_update_correlated_f64(const fk_kf_desc *d, const double *H, const double *R, const double *M, const double *z,
+                                const uint8_t *mask, double *x, double *P, double *y, double *K, double *S, double *SI,
+                                int32_t *status, void *stream)
+{
+    if (!d) return fail(FK_ERR_BAD_ARG, "desc is NULL");
+    if (d->n < 1 || d->n > 16 || d->m < 1 || d->m > 8) return fail(FK_ERR_UNSUPPORTED, "update_correlated: dim_x 1..16, dim_z 1..8");
+    if (d->layout != FK_LAYOUT_AOS && d->layout != FK_LAYOUT_SOA) return fail(FK_ERR_BAD_ARG, "update_correlated: bad layout");
+    if (d->model_mode != FK_MODEL_SHARED && d->model_mode != FK_MODEL_PER_TRACK)
+        return fail(FK_ERR_UNSUPPORTED, "update_correlated: M is shared or per track");
+    if (d->N < 0 || !H || !R || !M || !z || !x || !P) return fail(FK_ERR_BAD_ARG, "update_correlated: bad argument");
+    if (int rc = check_record_block((double)d->N, (double)d->n * d->n, FK_4GIB, "update_correlated: record block >= 4 GiB")) return rc;
+    if (d->N == 0) return FK_OK;
+    return launch_corr_update(d->n, d->m, (long)d->N, d->layout, H, R, M, d->model_mode == FK_MODEL_PER_TRACK, z, mask, x, P, y, K,
+                              S, SI, status, (hipStream_t)stream);
 }
 
 }  // extern "C"

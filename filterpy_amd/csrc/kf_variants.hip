@@ -11,19 +11,13 @@
 //                        P += K (Pn - Pb) K'
 // (update_sequential, kalman_filter.py:754-824, is the ordinary update on a slice of z, H, R and
 // runs on fk_kf_update_f64: host shim only.)
+// Kernels and their launchers only: the entry points are in kf_dispatch.cpp (fk_ukf_rts_correct_f64: ukf_dispatch.cpp).
 #include "fk_device.hpp"
 #include "fk_kernel_args.hpp"
+#include "fk_launchers.hpp"
 #include "../../include/filterhip.h"
 
 namespace fk {
-
-struct SteadyArgs {
-    const double *F, *H, *K, *B, *u, *z;
-    const uint8_t *mask;
-    double *x, *means, *means_p, *y_out;
-    long N, T;
-    int n, m, nu, k_per_track;
-};
 
 // F (NX x NX), H (NZ x NX) and the shared K (NX x NZ) sit in LDS; a per-track K in registers.
 // EXACT (n == NX, m == NZ): the x / z / y records move without per-element guards -- in NumPy order (AOS) as 16-byte
@@ -275,12 +269,6 @@ ukf_rts_kernel(int n, long N, const double *__restrict__ pPxb, const double *__r
     }
 }
 
-static int fail(int code, const char *msg)
-{
-    set_last_error(msg);
-    return code;
-}
-
 }  // namespace fk
 
 // dim_x 10 .. 16 of fk_ukf_rts_correct_f64: the same kernel on the padded classes 12 and 16, compiled in a unit of its own
@@ -340,7 +328,7 @@ int ukf_rts_big_launch(int n, long N, int layout, const double *Pxb, const doubl
 }
 }  // namespace fk
 #else
-using namespace fk;
+namespace fk {
 
 #define FK_BY_DIMS(n, m, CALL)                              \
     do {                                                    \
@@ -350,119 +338,83 @@ using namespace fk;
         else { CALL(9, 4); }                                \
     } while (0)
 
-extern "C" {
+// The launchers: each picks the instantiation of a call that its dispatcher has checked.
 
-int fk_kf_steadystate_f64(const fk_kf_desc *d, const double *F, const double *H, const double *K, const double *B,
-                          const double *u, const double *z, const uint8_t *mask, double *x, double *means,
-                          double *means_p, double *y_out, void *stream)
+int launch_steady(const SteadyArgs &a, int layout, hipStream_t s)
 {
-    if (!d) return fail(FK_ERR_BAD_ARG, "desc is NULL");
-    if (d->n < 1 || d->n > 16 || d->m < 1 || d->m > 8 || d->nu < 0 || d->nu > 4)
-        return fail(FK_ERR_UNSUPPORTED, "steady state: dim_x 1..16, dim_z 1..8, dim_u 0..4");
-    if (d->layout != FK_LAYOUT_AOS && d->layout != FK_LAYOUT_SOA) return fail(FK_ERR_BAD_ARG, "steady state: bad layout");
-    if (d->model_mode != FK_MODEL_SHARED && d->model_mode != FK_MODEL_PER_TRACK)
-        return fail(FK_ERR_UNSUPPORTED, "steady state: K is shared or per track");
-    if (d->N < 0 || d->T < 0 || !x || (!F && !z) || (z && (!H || !K)) || (d->nu > 0 && F && (!B || !u)))
-        return fail(FK_ERR_BAD_ARG, "steady state: bad argument");
-    if ((double)d->N * d->n * d->m * 8.0 >= 4294967296.0) return fail(FK_ERR_UNSUPPORTED, "steady state: record block >= 4 GiB");
-    if (d->N == 0 || d->T == 0) return FK_OK;
-    SteadyArgs a{};
-    a.F = F; a.H = H; a.K = K; a.B = (d->nu > 0 && F) ? B : nullptr; a.u = u; a.z = z; a.mask = mask;
-    a.x = x; a.means = means; a.means_p = means_p; a.y_out = y_out; a.N = d->N; a.T = d->T;
-    a.n = d->n; a.m = d->m; a.nu = d->nu; a.k_per_track = d->model_mode == FK_MODEL_PER_TRACK && K != nullptr;
     const dim3 grid((unsigned)((a.N + BLOCK - 1) / BLOCK)), block(BLOCK);
-    hipStream_t s = (hipStream_t)stream;
-    if (d->n > 9 || d->m > 4) {
+    if (a.n > 9 || a.m > 4) {
         // the padded classes (12,8), (16,8).  Round 4 ran them in the rolled unit (x and K in scratch: 0.12 / 0.08 of HBM at (16,8));
         // round 5: unrolled here -- only x moves, 512 multiply-adds per step at (16,8) -- with a shared gain read from LDS (KREG =
         // false), a per-track gain in registers.  FK_STEADY_ROLLED=1 keeps the rolled unit (A/B).
         static const bool rolled = [] { const char *v = getenv("FK_STEADY_ROLLED"); return v && v[0] == '1'; }();
-        if (rolled) return steady_big_launch(a, d->layout, s);
+        if (rolled) return steady_big_launch(a, layout, s);
 #define CALLB(NXV)                                                                                                           \
-        if (d->n == NXV && d->m == 8 && !a.k_per_track) {       /* the class's own shape: unguarded records, NumPy order through the LDS tiles */ \
-            if (d->layout == FK_LAYOUT_SOA) hipLaunchKernelGGL((steady_kernel<NXV, 8, LAYOUT_SOA, true, false>), grid, block, 0, s, a); \
+        if (a.n == NXV && a.m == 8 && !a.k_per_track) {         /* the class's own shape: unguarded records, NumPy order through the LDS tiles */ \
+            if (layout == FK_LAYOUT_SOA) hipLaunchKernelGGL((steady_kernel<NXV, 8, LAYOUT_SOA, true, false>), grid, block, 0, s, a); \
             else hipLaunchKernelGGL((steady_kernel<NXV, 8, LAYOUT_AOS, true, false>), grid, block, 0, s, a);                            \
         } else if (a.k_per_track) {                                                                                                     \
-            if (d->layout == FK_LAYOUT_SOA) hipLaunchKernelGGL((steady_kernel<NXV, 8, LAYOUT_SOA, false, true>), grid, block, 0, s, a); \
+            if (layout == FK_LAYOUT_SOA) hipLaunchKernelGGL((steady_kernel<NXV, 8, LAYOUT_SOA, false, true>), grid, block, 0, s, a); \
             else hipLaunchKernelGGL((steady_kernel<NXV, 8, LAYOUT_AOS, false, true>), grid, block, 0, s, a);                            \
-        } else if (d->layout == FK_LAYOUT_SOA) hipLaunchKernelGGL((steady_kernel<NXV, 8, LAYOUT_SOA, false, false>), grid, block, 0, s, a); \
+        } else if (layout == FK_LAYOUT_SOA) hipLaunchKernelGGL((steady_kernel<NXV, 8, LAYOUT_SOA, false, false>), grid, block, 0, s, a); \
         else if (aos_waves == 3) hipLaunchKernelGGL((steady_kernel<NXV, 8, LAYOUT_AOS, false, false, 3>), grid, block, 0, s, a);          \
         else hipLaunchKernelGGL((steady_kernel<NXV, 8, LAYOUT_AOS, false, false, 1>), grid, block, 0, s, a)
         // (the guarded NumPy-order records of the padded class are what costs registers: 512 VGPRs + 724 B of scratch at one wave per
         // SIMD, 168 + 2260 B at three; FK_STEADY_AOS_WAVES=1 / 3 picks, A/B in profiles/r05/dims/steady_big.jsonl)
         static const int aos_waves = [] { const char *v = getenv("FK_STEADY_AOS_WAVES"); return v && v[0] == '3' ? 3 : 1; }();
-        if (d->n <= 12) { CALLB(12); }
+        if (a.n <= 12) { CALLB(12); }
         else { CALLB(16); }
 #undef CALLB
         return check_launch("steady_kernel");
     }
 #define CALL(NXV, NZV)                                                                                      \
-    if (d->n == NXV && d->m == NZV) {                                                                                    \
-        if (d->layout == FK_LAYOUT_SOA) hipLaunchKernelGGL((steady_kernel<NXV, NZV, LAYOUT_SOA, true>), grid, block, 0, s, a); \
+    if (a.n == NXV && a.m == NZV) {                                                                                      \
+        if (layout == FK_LAYOUT_SOA) hipLaunchKernelGGL((steady_kernel<NXV, NZV, LAYOUT_SOA, true>), grid, block, 0, s, a); \
         else hipLaunchKernelGGL((steady_kernel<NXV, NZV, LAYOUT_AOS, true>), grid, block, 0, s, a);                       \
-    } else if (d->layout == FK_LAYOUT_SOA) hipLaunchKernelGGL((steady_kernel<NXV, NZV, LAYOUT_SOA, false>), grid, block, 0, s, a); \
+    } else if (layout == FK_LAYOUT_SOA) hipLaunchKernelGGL((steady_kernel<NXV, NZV, LAYOUT_SOA, false>), grid, block, 0, s, a); \
     else hipLaunchKernelGGL((steady_kernel<NXV, NZV, LAYOUT_AOS, false>), grid, block, 0, s, a)
     // exact instantiations for the shapes of BASELINE / the benches, the padded size classes for everything else
-    if (d->n == 2 && d->m == 1) { CALL(2, 1); }
-    else if (d->n == 6 && d->m == 3) { CALL(6, 3); }
-    else if (d->n == 9 && d->m == 3) { CALL(9, 3); }
-    else FK_BY_DIMS(d->n, d->m, CALL);
+    if (a.n == 2 && a.m == 1) { CALL(2, 1); }
+    else if (a.n == 6 && a.m == 3) { CALL(6, 3); }
+    else if (a.n == 9 && a.m == 3) { CALL(9, 3); }
+    else FK_BY_DIMS(a.n, a.m, CALL);
 #undef CALL
     return check_launch("steady_kernel");
 }
 
-int fk_kf_update_correlated_f64(const fk_kf_desc *d, const double *H, const double *R, const double *M,
-                                const double *z, const uint8_t *mask, double *x, double *P, double *y, double *K,
-                                double *S, double *SI, int32_t *status, void *stream)
+int launch_corr_update(int n, int m, long N, int layout, const double *H, const double *R, const double *M, int per_track,
+                       const double *z, const uint8_t *mask, double *x, double *P, double *y, double *K, double *S, double *SI,
+                       int32_t *status, hipStream_t s)
 {
-    if (!d) return fail(FK_ERR_BAD_ARG, "desc is NULL");
-    if (d->n < 1 || d->n > 16 || d->m < 1 || d->m > 8) return fail(FK_ERR_UNSUPPORTED, "update_correlated: dim_x 1..16, dim_z 1..8");
-    if (d->layout != FK_LAYOUT_AOS && d->layout != FK_LAYOUT_SOA) return fail(FK_ERR_BAD_ARG, "update_correlated: bad layout");
-    if (d->model_mode != FK_MODEL_SHARED && d->model_mode != FK_MODEL_PER_TRACK)
-        return fail(FK_ERR_UNSUPPORTED, "update_correlated: M is shared or per track");
-    if (d->N < 0 || !H || !R || !M || !z || !x || !P) return fail(FK_ERR_BAD_ARG, "update_correlated: bad argument");
-    if ((double)d->N * d->n * d->n * 8.0 >= 4294967296.0) return fail(FK_ERR_UNSUPPORTED, "update_correlated: record block >= 4 GiB");
-    if (d->N == 0) return FK_OK;
-    const dim3 grid((unsigned)((d->N + BLOCK - 1) / BLOCK)), block(BLOCK);
-    hipStream_t s = (hipStream_t)stream;
-    const int per_track = d->model_mode == FK_MODEL_PER_TRACK;
-    if (d->n > 9 || d->m > 4)                                                     // padded classes (12,8), (16,8): rolled unit
-        return corr_big_launch(d->n, d->m, (long)d->N, d->layout, H, R, M, per_track, z, mask, x, P, y, K, S, SI, status, s);
+    if (n > 9 || m > 4)                                                           // padded classes (12,8), (16,8): rolled unit
+        return corr_big_launch(n, m, N, layout, H, R, M, per_track, z, mask, x, P, y, K, S, SI, status, s);
+    const dim3 grid((unsigned)((N + BLOCK - 1) / BLOCK)), block(BLOCK);
 #define CALL(NXV, NZV)                                                                                          \
-    if (d->layout == FK_LAYOUT_SOA)                                                                             \
-        hipLaunchKernelGGL((corr_update_kernel<NXV, NZV, LAYOUT_SOA>), grid, block, 0, s, d->n, d->m, (long)d->N, \
+    if (layout == FK_LAYOUT_SOA)                                                                                \
+        hipLaunchKernelGGL((corr_update_kernel<NXV, NZV, LAYOUT_SOA>), grid, block, 0, s, n, m, N,              \
                            H, R, M, per_track, z, mask, x, P, y, K, S, SI, status);                              \
     else                                                                                                        \
-        hipLaunchKernelGGL((corr_update_kernel<NXV, NZV, LAYOUT_AOS>), grid, block, 0, s, d->n, d->m, (long)d->N, \
+        hipLaunchKernelGGL((corr_update_kernel<NXV, NZV, LAYOUT_AOS>), grid, block, 0, s, n, m, N,              \
                            H, R, M, per_track, z, mask, x, P, y, K, S, SI, status)
-    FK_BY_DIMS(d->n, d->m, CALL);
+    FK_BY_DIMS(n, m, CALL);
 #undef CALL
     return check_launch("corr_update_kernel");
 }
 
-int fk_ukf_rts_correct_f64(int32_t n, int64_t N, int32_t layout, const double *Pxb, const double *xb,
-                           const double *Pb, const double *xn, const double *Pn, double *x, double *P, double *K,
-                           int32_t *status, void *stream)
+int launch_ukf_rts_correct(int n, long N, int layout, const double *Pxb, const double *xb, const double *Pb, const double *xn,
+                           const double *Pn, double *x, double *P, double *K, int32_t *status, hipStream_t s)
 {
-    if (n < 1 || n > 16) return fail(FK_ERR_UNSUPPORTED, "ukf rts: dim_x 1..16");
-    if (layout != FK_LAYOUT_AOS && layout != FK_LAYOUT_SOA) return fail(FK_ERR_BAD_ARG, "ukf rts: bad layout");
-    if (N < 0 || !Pxb || !Pb || !xn || !Pn || !x || !P) return fail(FK_ERR_BAD_ARG, "ukf rts: bad argument");
-    if ((double)N * n * n * 8.0 >= 4294967296.0) return fail(FK_ERR_UNSUPPORTED, "ukf rts: record block >= 4 GiB");
-    if (N == 0) return FK_OK;
+    if (n > 9) return ukf_rts_big_launch(n, N, layout, Pxb, xb, Pb, xn, Pn, x, P, K, status, s);
     const dim3 grid((unsigned)((N + BLOCK - 1) / BLOCK)), block(BLOCK);
-    hipStream_t s = (hipStream_t)stream;
-    if (n > 9) return ukf_rts_big_launch(n, (long)N, layout, Pxb, xb, Pb, xn, Pn, x, P, K, status, s);
-#define CALL(NXV, NZV)                                                                                       \
-    if (layout == FK_LAYOUT_SOA)                                                                             \
-        hipLaunchKernelGGL((ukf_rts_kernel<NXV, LAYOUT_SOA>), grid, block, 0, s, n, (long)N, Pxb, xb, Pb, xn, \
-                           Pn, x, P, K, status);                                                             \
-    else                                                                                                     \
-        hipLaunchKernelGGL((ukf_rts_kernel<NXV, LAYOUT_AOS>), grid, block, 0, s, n, (long)N, Pxb, xb, Pb, xn, \
-                           Pn, x, P, K, status)
+#define CALL(NXV, NZV)                                                                                                      \
+    if (layout == FK_LAYOUT_SOA)                                                                                            \
+        hipLaunchKernelGGL((ukf_rts_kernel<NXV, LAYOUT_SOA>), grid, block, 0, s, n, N, Pxb, xb, Pb, xn, Pn, x, P, K, status); \
+    else                                                                                                                    \
+        hipLaunchKernelGGL((ukf_rts_kernel<NXV, LAYOUT_AOS>), grid, block, 0, s, n, N, Pxb, xb, Pb, xn, Pn, x, P, K, status)
     FK_BY_DIMS(n, 1, CALL);
 #undef CALL
     return check_launch("ukf_rts_kernel");
 }
 
-}  // extern "C"
+}  // namespace fk
 #endif   // FK_VARIANTS_BIG

@@ -1,12 +1,13 @@
 // ukf_kernels.hip -- fused linear-model unscented Kalman filter for gfx950 (MI355X).
 //
-//   fk_ukf_linear_batch_f64 <- UnscentedKalmanFilter.batch_filter (filterpy/kalman/UKF.py:524-632) with
-//                              fx(x, dt) = F x, hx(x) = H x: the whole predict (UKF.py:400-411) / update
-//                              (:462-481) loop stays in registers over the time steps.
-//   fk_ukf_linear_rts_f64   <- UnscentedKalmanFilter.rts_smoother (UKF.py:634-739), likewise.
-// FK_UKF_PART: the Makefile compiles this file eight times (parallel build) -- 1: forward kernels dim_x <= 6 + the forward
-// entry point, 2: forward dim_x 7..9, 3: smoother dim_x <= 6 + the smoother's entry point, 4: smoother dim_x 7..9; 5..8: the
-// same four sets of kernels with the sums regrouped over the +- pairs of sigma points (PAIRED, fk_ukf.hpp: the V4 steps).
+//   ukf_linear_kernel      <- UnscentedKalmanFilter.batch_filter (filterpy/kalman/UKF.py:524-632) with
+//                             fx(x, dt) = F x, hx(x) = H x: the whole predict (UKF.py:400-411) / update
+//                             (:462-481) loop stays in registers over the time steps.
+//   ukf_linear_rts_kernel  <- UnscentedKalmanFilter.rts_smoother (UKF.py:634-739), likewise.
+// Kernels and their launchers only: the entry points (fk_ukf_linear_batch_f64, fk_ukf_linear_rts_f64) are in ukf_dispatch.cpp.
+// FK_UKF_PART: the Makefile compiles this file eight times (parallel build) -- 1: forward kernels dim_x <= 6, 2: forward
+// dim_x 7..9, 3: smoother dim_x <= 6, 4: smoother dim_x 7..9; 5..8: the same four sets of kernels with the sums regrouped
+// over the +- pairs of sigma points (PAIRED, fk_ukf.hpp: the V4 steps).
 #include <stdlib.h>
 
 #ifndef FK_UKF_PART
@@ -18,9 +19,9 @@
 #define FK_UKF_RTS (FK_UKF_HAS(3) || FK_UKF_HAS(4) || FK_UKF_HAS(7) || FK_UKF_HAS(8) || FK_UKF_PART == 92)
 
 #include "../../include/filterhip.h"
-#include "fk_chunks.hpp"
 #include "fk_device.hpp"
 #include "fk_kernel_args.hpp"
+#include "fk_launchers.hpp"
 #include "fk_math_sym.hpp"
 #include "fk_ukf.hpp"
 
@@ -285,17 +286,8 @@ ukf_linear_kernel(const UkfArgs a_in, const double *__restrict__ pF, const doubl
 
 #endif
 
-// launchers of the instantiations this part holds (declared in every part)
-int ukf_fwd_launch_small(const UkfArgs &a, int layout, bool exact, hipStream_t s);    // classes (2,2), (4,2), (6,3)
-int ukf_fwd_launch_big(const UkfArgs &a, int layout, bool exact, hipStream_t s);      // classes (8,4), (9,3), (9,4)
-int ukf_rts_launch_small(const UkfRtsArgs &a, const double *F, const double *Q, const double *Wm, const double *Wc, int layout, bool exact, hipStream_t s);   // 2, 4, 6
-int ukf_rts_launch_big(const UkfRtsArgs &a, const double *F, const double *Q, const double *Wm, const double *Wc, int layout, bool exact, hipStream_t s);     // 8, 9
-// ... and of their PAIRED twins (parts 5..8)
-int ukf_fwd_launch_small_paired(const UkfArgs &a, int layout, bool exact, hipStream_t s);
-int ukf_fwd_launch_big_paired(const UkfArgs &a, int layout, bool exact, hipStream_t s);
-int ukf_rts_launch_small_paired(const UkfRtsArgs &a, const double *F, const double *Q, const double *Wm, const double *Wc, int layout, bool exact, hipStream_t s);
-int ukf_rts_launch_big_paired(const UkfRtsArgs &a, const double *F, const double *Q, const double *Wm, const double *Wc, int layout, bool exact, hipStream_t s);
-
+// The launchers of the instantiations this part holds (declared in fk_launchers.hpp): ukf_fwd_launch_small -- the classes (2,2),
+// (4,2), (6,3) --, _big -- (8,4), (9,3), (9,4) --, ukf_rts_launch_small -- 2, 4, 6 --, _big -- 8, 9 -- and their PAIRED twins.
 #if FK_UKF_FWD
 #define FK_UKF_GO(NXV, NZV)                                                                                      \
     do {                                                                                                         \
@@ -766,199 +758,4 @@ int ukf_rts_launch_big_paired(const UkfRtsArgs &a, const double *F, const double
 #undef FK_UKF_GO
 
 #endif
-// ukf_mlg.hip, one object per dim_x
-#define FK_UMLG_DECL(NXV)                                         \
-    int launch_ukf_mlg_##NXV(const UkfArgs &, int, hipStream_t); \
-    int launch_ukf_mlg_rts_##NXV(const UkfRtsArgs &, const double *, const double *, const double *, const double *, int, hipStream_t);
-FK_UMLG_DECL(7) FK_UMLG_DECL(8) FK_UMLG_DECL(9) FK_UMLG_DECL(10) FK_UMLG_DECL(11) FK_UMLG_DECL(12) FK_UMLG_DECL(13) FK_UMLG_DECL(14) FK_UMLG_DECL(15) FK_UMLG_DECL(16)
-#undef FK_UMLG_DECL
-#if FK_UKF_HAS(1)
-static int ukf_mlg_launch(const UkfArgs &a, int layout, hipStream_t s)
-{
-    int rc = 1;
-    switch (a.n) {
-        case 7: rc = launch_ukf_mlg_7(a, layout, s); break;
-        case 8: rc = launch_ukf_mlg_8(a, layout, s); break;
-        case 9: rc = launch_ukf_mlg_9(a, layout, s); break;
-        case 10: rc = launch_ukf_mlg_10(a, layout, s); break;
-        case 11: rc = launch_ukf_mlg_11(a, layout, s); break;
-        case 12: rc = launch_ukf_mlg_12(a, layout, s); break;
-        case 13: rc = launch_ukf_mlg_13(a, layout, s); break;
-        case 14: rc = launch_ukf_mlg_14(a, layout, s); break;
-        case 15: rc = launch_ukf_mlg_15(a, layout, s); break;
-        case 16: rc = launch_ukf_mlg_16(a, layout, s); break;
-        default: break;
-    }
-    if (rc == 1) {
-        set_last_error("fused linear UKF: no four-lane instantiation for these dims");
-        return FK_ERR_UNSUPPORTED;
-    }
-    return rc;
-}
-#endif
-
-#if FK_UKF_HAS(3)
-static int ukf_mlg_rts_launch(const UkfRtsArgs &a, const double *F, const double *Q, const double *Wm, const double *Wc, int layout, hipStream_t s)
-{
-    int rc = 1;
-    switch (a.n) {
-        case 7: rc = launch_ukf_mlg_rts_7(a, F, Q, Wm, Wc, layout, s); break;
-        case 8: rc = launch_ukf_mlg_rts_8(a, F, Q, Wm, Wc, layout, s); break;
-        case 9: rc = launch_ukf_mlg_rts_9(a, F, Q, Wm, Wc, layout, s); break;
-        case 10: rc = launch_ukf_mlg_rts_10(a, F, Q, Wm, Wc, layout, s); break;
-        case 11: rc = launch_ukf_mlg_rts_11(a, F, Q, Wm, Wc, layout, s); break;
-        case 12: rc = launch_ukf_mlg_rts_12(a, F, Q, Wm, Wc, layout, s); break;
-        case 13: rc = launch_ukf_mlg_rts_13(a, F, Q, Wm, Wc, layout, s); break;
-        case 14: rc = launch_ukf_mlg_rts_14(a, F, Q, Wm, Wc, layout, s); break;
-        case 15: rc = launch_ukf_mlg_rts_15(a, F, Q, Wm, Wc, layout, s); break;
-        case 16: rc = launch_ukf_mlg_rts_16(a, F, Q, Wm, Wc, layout, s); break;
-        default: break;
-    }
-    if (rc == 1) {
-        set_last_error("fused linear UKF smoother: no four-lane instantiation for this dim_x");
-        return FK_ERR_UNSUPPORTED;
-    }
-    return rc;
-}
-#endif
-
-// Which calls the several-lanes-per-track kernels (ukf_mlg.hip) serve, decided by measurement (profiles/r05/ukf_mlg/):
-//   filter:   dim_x 10..16 (no one-lane kernel exists there); at 7..9 the one-lane classes are faster (8: 1.9 vs 2.8 ms, 9: 2.2
-//             vs 4.4 ms at N = 1e5, T = 100) and keep the call;
-//   smoother: dim_x 10..16, and 7..9 too for pair-weight callers (8: 5.1 / 8.2 -> 4.4 / 4.1 ms, 9: 10.3 / 13.8 -> 7.8 / 7.4 ms
-//             element-major / NumPy order): the one-lane smoother classes run one wave per SIMD with 0.4-1.3 KB of scratch.
-// A/B knobs, read once per process: FK_UKF_MLG=0 takes the several-lane kernels out altogether (dim_x >= 10 then answers
-// FK_ERR_UNSUPPORTED and the host takes the building blocks); FK_UKF_MLG_MIN_NX / FK_UKF_MLG_RTS_MIN_NX = 7..10 move the
-// filter's / the smoother's lower bound.
-// (ONE snapshot of the environment for the whole library -- fk_host.cpp: this file is compiled as eight objects, and a copy per
-// object, each initialised at its own first call, let fk_ukf_linear_supported and the launchers disagree when a knob changed in
-// between)
-struct UkfMlgRoute { int fwd_min, rts_min; };
-UkfMlgRoute ukf_mlg_route();
-static int ukf_mlg_min_nx() { return ukf_mlg_route().fwd_min; }
-static int ukf_mlg_rts_min_nx() { return ukf_mlg_route().rts_min; }
-
-static int fail(int code, const char *msg)
-{
-    set_last_error(msg);
-    return code;
-}
-
-// FK_UKF_PADDED=1: the padded instantiations also at the exact dims (A/B, and the parity tests of the padded path)
-static bool ukf_exact()
-{
-    static const bool padded = [] { const char *v = getenv("FK_UKF_PADDED"); return v && v[0] == '1'; }();
-    return !padded;
-}
-
-// The pair-regrouped kernels run when the caller asserts weights equal within every +- pair (FK_UKF_FLAG_PAIR_WEIGHTS);
-// FK_UKF_PAIRED=0 keeps the index-order sums for every call (A/B, and the parity tests of that path).
-static bool ukf_paired(const fk_ukf_desc *d)
-{
-    static const bool off = [] { const char *v = getenv("FK_UKF_PAIRED"); return v && v[0] == '0'; }();
-    return !off && (d->flags & FK_UKF_FLAG_PAIR_WEIGHTS) != 0;
-}
-
 }  // namespace fk
-
-using namespace fk;
-
-extern "C" {
-
-#if FK_UKF_HAS(1)
-int fk_ukf_linear_supported(int32_t n, int32_t m, int32_t flags, int32_t smoother)
-{
-    const bool pairw = (flags & FK_UKF_FLAG_PAIR_WEIGHTS) != 0;
-    if (smoother) {
-        if (n >= 10 && n <= 16) return pairw && ukf_mlg_rts_min_nx() <= 10;
-        return n >= 1 && n <= 9;
-    }
-    if (n >= 10 && n <= 16) return m >= 1 && m <= 8 && pairw && ukf_mlg_min_nx() <= 10;
-    return (n >= 1 && n <= 6 && m >= 1 && m <= 3) || (n >= 7 && n <= 9 && m >= 1 && m <= 4);
-}
-#endif
-
-#if FK_UKF_HAS(1)
-int fk_ukf_linear_batch_f64(const fk_ukf_desc *d, const double *F, const double *H, const double *Q,
-                            const double *R, const double *Wm, const double *Wc, const double *z,
-                            const uint8_t *mask, double *x, double *P, double *means, double *covs,
-                            int32_t *status, void *stream)
-{
-    if (!d) return fail(FK_ERR_BAD_ARG, "desc is NULL");
-    // dim_x 10..16 (dim_z 1..8): four / eight lanes per track (ukf_mlg.hip), the pair-regrouped sums only
-    const bool big = d->n >= 10 && d->n <= 16 && d->m >= 1 && d->m <= 8;
-    const bool quad = big || (d->n >= ukf_mlg_min_nx() && d->n <= 9 && d->m >= 1 && d->m <= 4 && (d->flags & FK_UKF_FLAG_PAIR_WEIGHTS) && ukf_paired(d));
-    if (big) {
-        if (ukf_mlg_min_nx() > 10 || !(d->flags & FK_UKF_FLAG_PAIR_WEIGHTS))
-            return fail(FK_ERR_UNSUPPORTED, "fused linear UKF at dim_x 10..16: needs weights equal within every +- pair (FK_UKF_FLAG_PAIR_WEIGHTS; and FK_UKF_MLG != 0)");
-    } else if (d->n < 1 || d->n > 9 || d->m < 1 || d->m > 4 || (d->n <= 6 && d->m > 3))
-        return fail(FK_ERR_UNSUPPORTED, "fused linear UKF: dim_x 1..6 with dim_z 1..3, dim_x 7..9 with dim_z 1..4, dim_x 10..16 with dim_z 1..8");
-    if (d->N < 0 || d->T < 0 || !F || !H || !Q || !R || !Wm || !Wc || !z || !x || !P)
-        return fail(FK_ERR_BAD_ARG, "fused linear UKF: bad argument");
-    if ((double)d->N * d->n * d->n * 8.0 >= 4294967296.0 - 32.0) return fail(FK_ERR_UNSUPPORTED, "fused linear UKF: record block >= 4 GiB, split the batch");
-    if (d->N == 0 || d->T == 0) return FK_OK;
-    UkfArgs a0{};
-    a0.F = F; a0.H = H; a0.Q = Q; a0.R = R; a0.Wm = Wm; a0.Wc = Wc; a0.z = z; a0.mask = mask;
-    a0.x = x; a0.P = P; a0.means = means; a0.covs = covs; a0.status = status;
-    a0.N = d->N; a0.T = d->T; a0.n = d->n; a0.m = d->m; a0.scale = d->scale;
-    a0.i0 = 0; a0.cnt = d->N; a0.status_or = 0;
-    {   // FK_UKF_SOA_PAIRS=0: the element-major outputs as 8-byte stores everywhere (A/B)
-        const char *pv = getenv("FK_UKF_SOA_PAIRS");
-        a0.soa_pairs = !(pv && pv[0] == '0');
-    }
-    const int layout = d->layout;
-    const bool exact = ukf_exact(), paired = ukf_paired(d);
-    // one piece: tracks [a.i0, a.i0 + a.cnt), a.T steps from the pointers in a.  Classes (2,2), (4,2), (6,3), (8,4), (9,3),
-    // (9,4): the exact instantiation where the dims are the class's own, the padded one otherwise.
-    auto one = [&](const UkfArgs &a, hipStream_t s) -> int {
-        if (quad) return ukf_mlg_launch(a, layout, s);
-        if (paired) return (a.n <= 6 && a.m <= 3) ? ukf_fwd_launch_small_paired(a, layout, exact, s) : ukf_fwd_launch_big_paired(a, layout, exact, s);
-        return (a.n <= 6 && a.m <= 3) ? ukf_fwd_launch_small(a, layout, exact, s) : ukf_fwd_launch_big(a, layout, exact, s);
-    };
-    // tail filling (fk_chunks.hpp): FK_UKF_CHUNKS="G,H" cuts the call into G track groups x H time chunks on G streams, the
-    // state handed from chunk to chunk through x / P in place (bit-identical results).  Default: one launch -- at
-    // BASELINE configs[3] (1563 waves for 2048 wave slots) there is no last round to fill, and the forced decompositions
-    // measured no faster (profiles/r03/ukf_chunking.jsonl).
-    return ukf_chunked_call(a0, a0.n, a0.m, one, (hipStream_t)stream);
-}
-#endif
-
-#if FK_UKF_HAS(3)
-int fk_ukf_linear_rts_f64(const fk_ukf_desc *d, const double *F, const double *Q, const double *Wm, const double *Wc,
-                          const double *Xs, const double *Ps, double *xs, double *Ps_out, double *K, int32_t *status,
-                          void *stream)
-{
-    if (!d) return fail(FK_ERR_BAD_ARG, "desc is NULL");
-    // dim_x 10..16 -- and 7..9 for pair-weight callers (ukf_mlg_route) --: four / eight lanes per track (ukf_mlg.hip), pair-regrouped sums only
-    const bool big = d->n >= 10 && d->n <= 16;
-    const bool quad = big || (d->n >= ukf_mlg_rts_min_nx() && d->n <= 9 && (d->flags & FK_UKF_FLAG_PAIR_WEIGHTS) && ukf_paired(d));
-    if (big) {
-        if (ukf_mlg_rts_min_nx() > 10 || !(d->flags & FK_UKF_FLAG_PAIR_WEIGHTS))
-            return fail(FK_ERR_UNSUPPORTED, "fused linear UKF smoother at dim_x 10..16: needs weights equal within every +- pair (FK_UKF_FLAG_PAIR_WEIGHTS; and FK_UKF_MLG != 0)");
-    } else if (d->n < 1 || d->n > 9) return fail(FK_ERR_UNSUPPORTED, "fused linear UKF smoother: dim_x 1..9, 10..16");
-    if (quad && (double)d->N * d->n * d->n * 8.0 >= 4294967296.0 - 32.0) return fail(FK_ERR_UNSUPPORTED, "fused linear UKF smoother: record block >= 4 GiB, split the batch");
-    if (d->N < 0 || d->T < 0 || !F || !Q || !Wm || !Wc || !Xs || !Ps || !xs || !Ps_out)
-        return fail(FK_ERR_BAD_ARG, "fused linear UKF smoother: bad argument");
-    if ((double)d->N * d->n * d->n * 8.0 >= 4294967296.0) return fail(FK_ERR_UNSUPPORTED, "fused linear UKF smoother: record block >= 4 GiB, split the batch");
-    if (d->N == 0 || d->T == 0) return FK_OK;
-    UkfRtsArgs a0{};
-    a0.Xs = Xs; a0.Ps = Ps; a0.xs = xs; a0.ps = Ps_out; a0.Ks = K; a0.status = status;
-    a0.N = d->N; a0.T = d->T; a0.n = d->n; a0.scale = d->scale;
-    a0.i0 = 0; a0.cnt = d->N; a0.cont = 0; a0.status_or = 0;
-    const int layout = d->layout;
-    if (quad) return d->T >= 1 ? ukf_mlg_rts_launch(a0, F, Q, Wm, Wc, layout, (hipStream_t)stream) : FK_OK;
-    const bool exact = ukf_exact(), paired = ukf_paired(d);
-    auto one = [&](const UkfRtsArgs &a, hipStream_t s) -> int {
-        if (paired) return a.n <= 6 ? ukf_rts_launch_small_paired(a, F, Q, Wm, Wc, layout, exact, s) : ukf_rts_launch_big_paired(a, F, Q, Wm, Wc, layout, exact, s);
-        return a.n <= 6 ? ukf_rts_launch_small(a, F, Q, Wm, Wc, layout, exact, s) : ukf_rts_launch_big(a, F, Q, Wm, Wc, layout, exact, s);
-    };
-    // Tail filling (fk_chunks.hpp): the classes of dim_x >= 5 run one wave per SIMD, so BASELINE configs[3]'s 1563 waves are
-    // two rounds for 1.53 rounds of work; cut into track groups x backward time windows on helper streams the pieces of
-    // different groups fill each other's tails (bit-identical results: a window's top step is read back from the smoothed
-    // outputs).  FK_UKF_RTS_CHUNKS="G,H" forces a decomposition ("1,1": one launch).
-    const long slots = 1024L * (d->n <= 2 ? 4 : d->n <= 4 ? 2 : 1);
-    return ukf_rts_chunked_call(a0, a0.n, slots, one, (hipStream_t)stream);
-}
-#endif
-
-}  // extern "C"

@@ -2,11 +2,12 @@
 //
 // One track per lane.  Stand-alone kernels mirror the reference's building blocks so
 // that a UKF with arbitrary (host-side, vectorised) fx/hx can be assembled from them:
-//   fk_ut_sigma_points_f64   <- MerweScaledSigmaPoints.sigma_points (sigma_points.py:124-177)
-//                               JulierSigmaPoints.sigma_points      (sigma_points.py:289-357)
-//   fk_ut_transform_f64      <- unscented_transform (unscented_transform.py:99-128)
-//   fk_ut_cross_variance_f64 <- UnscentedKalmanFilter.cross_variance (UKF.py:493-504)
-// (the fused linear-model filter lives in ukf_kernels.hip)
+//   sigma_kernel, sigma_coop_kernel         <- MerweScaledSigmaPoints.sigma_points (sigma_points.py:124-177)
+//                                              JulierSigmaPoints.sigma_points      (sigma_points.py:289-357)
+//   ut_kernel, ut_reg_kernel, ut_coop_kernel <- unscented_transform (unscented_transform.py:99-128)
+//   cross_kernel                            <- UnscentedKalmanFilter.cross_variance (UKF.py:493-504)
+// Kernels and their launchers only: the entry points (fk_ut_*_f64, fk_ukf_correct_f64) are in ukf_dispatch.cpp; the fused
+// linear-model filter lives in ukf_kernels.hip.
 // Algorithmic bytes: sigma points 8(n + n^2 + (2n+1)n), UT 8((2n+1)n + n + n^2) per track;
 // fused step 8(m + n + n^2) per track-step.
 #include <stdlib.h>
@@ -14,6 +15,7 @@
 #include "../../include/filterhip.h"
 #include "fk_device.hpp"
 #include "fk_kernel_args.hpp"
+#include "fk_launchers.hpp"
 #include "fk_math_sym.hpp"
 
 // FK_UT_PART: the Makefile compiles this file twice (1: sigma points + transform, 2: cross variance +
@@ -347,16 +349,6 @@ ukf_correct_kernel(int n, int m, long N, const double *__restrict__ pPxz, const 
     }
 }
 
-static int fail(int code, const char *msg)
-{
-    set_last_error(msg);
-    return code;
-}
-
-}  // namespace fk
-
-using namespace fk;
-
 #define FK_BY_NX(n, CALL)            \
     do {                             \
         if ((n) <= 2) { CALL(2); }   \
@@ -367,122 +359,93 @@ using namespace fk;
         else { CALL(16); }           \
     } while (0)
 
-extern "C" {
+// The launchers: each picks the instantiation of a call that ukf_dispatch.cpp has checked.
 
 #if FK_UT_PART != 2
-int fk_ut_sigma_points_f64(int32_t n, int64_t N, int32_t layout, double scale, const double *x,
-                           const double *P, double *sigmas, int32_t *status, void *stream)
+int launch_ut_points(int n, long N, int layout, double scale, const double *x, const double *P, double *sigmas, int32_t *status,
+                     hipStream_t stream)
 {
-    if (n < 1 || n > 16) return fail(FK_ERR_UNSUPPORTED, "sigma points: dim_x must be 1..16");
-    if (N < 0 || !x || !P || !sigmas) return fail(FK_ERR_BAD_ARG, "sigma points: bad argument");
-    if ((double)N * (2 * n + 1) * n * 8.0 >= 4294967296.0) return fail(FK_ERR_UNSUPPORTED, "sigma points: record block >= 4 GiB, split the batch");
-    if (N == 0) return FK_OK;
     const dim3 grid((unsigned)((N + BLOCK - 1) / BLOCK)), block(BLOCK);
     // NumPy order at the exact dims 2 / 4 / 6: the wave-cooperative kernel (FK_UT_COOP=0: the per-lane 16-byte pairs of round 2)
     static const bool coop = [] { const char *v = getenv("FK_UT_COOP"); return !(v && v[0] == '0'); }();
     if (coop && layout == FK_LAYOUT_AOS && (n == 2 || n == 4 || n == 6)) {
         const dim3 g1((unsigned)((N + UT_WAVE - 1) / UT_WAVE)), b1(UT_WAVE);
-        if (n == 2) hipLaunchKernelGGL((sigma_coop_kernel<2>), g1, b1, 0, (hipStream_t)stream, (long)N, scale, x, P, sigmas, status);
-        else if (n == 4) hipLaunchKernelGGL((sigma_coop_kernel<4>), g1, b1, 0, (hipStream_t)stream, (long)N, scale, x, P, sigmas, status);
-        else hipLaunchKernelGGL((sigma_coop_kernel<6>), g1, b1, 0, (hipStream_t)stream, (long)N, scale, x, P, sigmas, status);
+        if (n == 2) hipLaunchKernelGGL((sigma_coop_kernel<2>), g1, b1, 0, stream, N, scale, x, P, sigmas, status);
+        else if (n == 4) hipLaunchKernelGGL((sigma_coop_kernel<4>), g1, b1, 0, stream, N, scale, x, P, sigmas, status);
+        else hipLaunchKernelGGL((sigma_coop_kernel<6>), g1, b1, 0, stream, N, scale, x, P, sigmas, status);
         return check_launch("sigma_coop_kernel");
     }
-#define CALL(NXV)                                                                                      \
-    if (layout == FK_LAYOUT_SOA)                                                                       \
-        hipLaunchKernelGGL((sigma_kernel<NXV, LAYOUT_SOA>), grid, block, 0, (hipStream_t)stream, n, N, \
-                           scale, x, P, sigmas, status);                                               \
-    else if (n == NXV && NXV <= 8)                                                                     \
-        hipLaunchKernelGGL((sigma_kernel<NXV, LAYOUT_AOS, true>), grid, block, 0, (hipStream_t)stream, n, N, \
-                           scale, x, P, sigmas, status);                                               \
-    else                                                                                               \
-        hipLaunchKernelGGL((sigma_kernel<NXV, LAYOUT_AOS>), grid, block, 0, (hipStream_t)stream, n, N, \
-                           scale, x, P, sigmas, status)
+#define CALL(NXV)                                                                                                         \
+    if (layout == FK_LAYOUT_SOA)                                                                                          \
+        hipLaunchKernelGGL((sigma_kernel<NXV, LAYOUT_SOA>), grid, block, 0, stream, n, N, scale, x, P, sigmas, status);   \
+    else if (n == NXV && NXV <= 8)                                                                                        \
+        hipLaunchKernelGGL((sigma_kernel<NXV, LAYOUT_AOS, true>), grid, block, 0, stream, n, N, scale, x, P, sigmas, status); \
+    else                                                                                                                  \
+        hipLaunchKernelGGL((sigma_kernel<NXV, LAYOUT_AOS>), grid, block, 0, stream, n, N, scale, x, P, sigmas, status)
     FK_BY_NX(n, CALL);
 #undef CALL
     return check_launch("sigma_kernel");
 }
 
-int fk_ut_transform_f64(int32_t n, int32_t k, int64_t N, int32_t layout, const double *sigmas,
-                        const double *Wm, const double *Wc, const double *noise_cov, double *x_out,
-                        double *P_out, void *stream)
+int launch_ut_transform(int n, int k, long N, int layout, const double *sigmas, const double *Wm, const double *Wc,
+                        const double *noise_cov, double *x_out, double *P_out, hipStream_t stream)
 {
-    if (n < 1 || n > 16 || k < 1) return fail(FK_ERR_UNSUPPORTED, "unscented transform: dim must be 1..16");
-    if (N < 0 || !sigmas || !Wm || !Wc || !x_out || !P_out) return fail(FK_ERR_BAD_ARG, "unscented transform: bad argument");
-    if ((double)N * k * n * 8.0 >= 4294967296.0) return fail(FK_ERR_UNSUPPORTED, "unscented transform: record block >= 4 GiB, split the batch");
-    if (N == 0) return FK_OK;
     const dim3 grid((unsigned)((N + BLOCK - 1) / BLOCK)), block(BLOCK);
     static const bool coop = [] { const char *v = getenv("FK_UT_COOP"); return !(v && v[0] == '0'); }();
     if (coop && layout == FK_LAYOUT_AOS && k == 2 * n + 1 && (n == 2 || n == 4 || n == 6)) {
         const dim3 g1((unsigned)((N + UT_WAVE - 1) / UT_WAVE)), b1(UT_WAVE);
-        if (n == 2) hipLaunchKernelGGL((ut_coop_kernel<2>), g1, b1, 0, (hipStream_t)stream, (long)N, sigmas, Wm, Wc, noise_cov, x_out, P_out);
-        else if (n == 4) hipLaunchKernelGGL((ut_coop_kernel<4>), g1, b1, 0, (hipStream_t)stream, (long)N, sigmas, Wm, Wc, noise_cov, x_out, P_out);
-        else hipLaunchKernelGGL((ut_coop_kernel<6>), g1, b1, 0, (hipStream_t)stream, (long)N, sigmas, Wm, Wc, noise_cov, x_out, P_out);
+        if (n == 2) hipLaunchKernelGGL((ut_coop_kernel<2>), g1, b1, 0, stream, N, sigmas, Wm, Wc, noise_cov, x_out, P_out);
+        else if (n == 4) hipLaunchKernelGGL((ut_coop_kernel<4>), g1, b1, 0, stream, N, sigmas, Wm, Wc, noise_cov, x_out, P_out);
+        else hipLaunchKernelGGL((ut_coop_kernel<6>), g1, b1, 0, stream, N, sigmas, Wm, Wc, noise_cov, x_out, P_out);
         return check_launch("ut_coop_kernel");
     }
     if (k == 2 * n + 1 && (n == 2 || n == 4 || n == 6)) {
-#define REG(NXV)                                                                                          \
-    if (layout == FK_LAYOUT_SOA)                                                                          \
-        hipLaunchKernelGGL((ut_reg_kernel<NXV, LAYOUT_SOA>), grid, block, 0, (hipStream_t)stream, (long)N, \
-                           sigmas, Wm, Wc, noise_cov, x_out, P_out);                                      \
-    else                                                                                                  \
-        hipLaunchKernelGGL((ut_reg_kernel<NXV, LAYOUT_AOS>), grid, block, 0, (hipStream_t)stream, (long)N, \
-                           sigmas, Wm, Wc, noise_cov, x_out, P_out)
+#define REG(NXV)                                                                                                           \
+    if (layout == FK_LAYOUT_SOA)                                                                                           \
+        hipLaunchKernelGGL((ut_reg_kernel<NXV, LAYOUT_SOA>), grid, block, 0, stream, N, sigmas, Wm, Wc, noise_cov, x_out, P_out); \
+    else                                                                                                                   \
+        hipLaunchKernelGGL((ut_reg_kernel<NXV, LAYOUT_AOS>), grid, block, 0, stream, N, sigmas, Wm, Wc, noise_cov, x_out, P_out)
         if (n == 2) { REG(2); }
         else if (n == 4) { REG(4); }
         else { REG(6); }
 #undef REG
         return check_launch("ut_reg_kernel");
     }
-#define CALL(NXV)                                                                                   \
-    if (layout == FK_LAYOUT_SOA)                                                                    \
-        hipLaunchKernelGGL((ut_kernel<NXV, LAYOUT_SOA>), grid, block, 0, (hipStream_t)stream, n, k, \
-                           N, sigmas, Wm, Wc, noise_cov, x_out, P_out);                             \
-    else                                                                                            \
-        hipLaunchKernelGGL((ut_kernel<NXV, LAYOUT_AOS>), grid, block, 0, (hipStream_t)stream, n, k, \
-                           N, sigmas, Wm, Wc, noise_cov, x_out, P_out)
+#define CALL(NXV)                                                                                                          \
+    if (layout == FK_LAYOUT_SOA)                                                                                           \
+        hipLaunchKernelGGL((ut_kernel<NXV, LAYOUT_SOA>), grid, block, 0, stream, n, k, N, sigmas, Wm, Wc, noise_cov, x_out, P_out); \
+    else                                                                                                                   \
+        hipLaunchKernelGGL((ut_kernel<NXV, LAYOUT_AOS>), grid, block, 0, stream, n, k, N, sigmas, Wm, Wc, noise_cov, x_out, P_out)
     FK_BY_NX(n, CALL);
 #undef CALL
     return check_launch("ut_kernel");
 }
-
 #endif   // FK_UT_PART
+
 #if FK_UT_PART != 1
-int fk_ut_cross_variance_f64(int32_t n, int32_t m, int32_t k, int64_t N, int32_t layout,
-                             const double *x, const double *z, const double *sigmas_f,
-                             const double *sigmas_h, const double *Wc, double *Pxz, void *stream)
+int launch_ut_cross(int n, int m, int k, long N, int layout, const double *x, const double *z, const double *sigmas_f,
+                    const double *sigmas_h, const double *Wc, double *Pxz, hipStream_t stream)
 {
-    if (n < 1 || n > 16 || m < 1 || k < 1) return fail(FK_ERR_UNSUPPORTED, "cross variance: dim_x must be 1..16");
-    if (N < 0 || !sigmas_f || !sigmas_h || !Wc || !Pxz) return fail(FK_ERR_BAD_ARG, "cross variance: bad argument");
-    if ((double)N * k * (n > m ? n : m) * 8.0 >= 4294967296.0) return fail(FK_ERR_UNSUPPORTED, "cross variance: record block >= 4 GiB, split the batch");
-    if (N == 0) return FK_OK;
     const dim3 grid((unsigned)((N + BLOCK - 1) / BLOCK)), block(BLOCK);
-#define CALL(NXV)                                                                                      \
-    if (layout == FK_LAYOUT_SOA)                                                                       \
-        hipLaunchKernelGGL((cross_kernel<NXV, LAYOUT_SOA>), grid, block, 0, (hipStream_t)stream, n, m, \
-                           k, N, x, z, sigmas_f, sigmas_h, Wc, Pxz);                                   \
-    else                                                                                               \
-        hipLaunchKernelGGL((cross_kernel<NXV, LAYOUT_AOS>), grid, block, 0, (hipStream_t)stream, n, m, \
-                           k, N, x, z, sigmas_f, sigmas_h, Wc, Pxz)
+#define CALL(NXV)                                                                                                          \
+    if (layout == FK_LAYOUT_SOA)                                                                                           \
+        hipLaunchKernelGGL((cross_kernel<NXV, LAYOUT_SOA>), grid, block, 0, stream, n, m, k, N, x, z, sigmas_f, sigmas_h, Wc, Pxz); \
+    else                                                                                                                   \
+        hipLaunchKernelGGL((cross_kernel<NXV, LAYOUT_AOS>), grid, block, 0, stream, n, m, k, N, x, z, sigmas_f, sigmas_h, Wc, Pxz)
     FK_BY_NX(n, CALL);
 #undef CALL
     return check_launch("cross_kernel");
 }
 
-int fk_ut_linear_map_f64(int32_t n_in, int32_t n_out, int32_t k, int64_t N, int32_t layout, const double *M,
-                         const double *in, double *out, void *stream)
+int launch_ut_linear_map(int n_in, int n_out, int k, long N, int layout, const double *M, const double *in, double *out,
+                         hipStream_t stream)
 {
-    if (n_in < 1 || n_in > 16 || n_out < 1 || n_out > 16 || k < 1) return fail(FK_ERR_UNSUPPORTED, "linear map: dims must be 1..16");
-    if (N < 0 || !M || !in || !out) return fail(FK_ERR_BAD_ARG, "linear map: bad argument");
-    if ((double)N * k * (n_in > n_out ? n_in : n_out) * 8.0 >= 4294967296.0) return fail(FK_ERR_UNSUPPORTED, "linear map: record block >= 4 GiB, split the batch");
-    if (N == 0) return FK_OK;
     const dim3 grid((unsigned)((N + BLOCK - 1) / BLOCK)), block(BLOCK);
-#define CALL(NXV)                                                                                                \
-    if (layout == FK_LAYOUT_SOA)                                                                                 \
-        hipLaunchKernelGGL((linear_map_kernel<NXV, LAYOUT_SOA>), grid, block, 0, (hipStream_t)stream, n_in, n_out, k, \
-                           (long)N, M, in, out);                                                                 \
-    else                                                                                                         \
-        hipLaunchKernelGGL((linear_map_kernel<NXV, LAYOUT_AOS>), grid, block, 0, (hipStream_t)stream, n_in, n_out, k, \
-                           (long)N, M, in, out)
+#define CALL(NXV)                                                                                                          \
+    if (layout == FK_LAYOUT_SOA)                                                                                           \
+        hipLaunchKernelGGL((linear_map_kernel<NXV, LAYOUT_SOA>), grid, block, 0, stream, n_in, n_out, k, N, M, in, out);   \
+    else                                                                                                                   \
+        hipLaunchKernelGGL((linear_map_kernel<NXV, LAYOUT_AOS>), grid, block, 0, stream, n_in, n_out, k, N, M, in, out)
     if (n_in <= 4) { CALL(4); }
     else if (n_in <= 8) { CALL(8); }
     else { CALL(16); }
@@ -490,23 +453,15 @@ int fk_ut_linear_map_f64(int32_t n_in, int32_t n_out, int32_t k, int64_t N, int3
     return check_launch("linear_map_kernel");
 }
 
-int fk_ukf_correct_f64(int32_t n, int32_t m, int64_t N, int32_t layout, const double *Pxz, const double *zp,
-                       const double *S, const double *z, double *x, double *P, double *K, int32_t *status,
-                       void *stream)
+int launch_ukf_correct(int n, int m, long N, int layout, const double *Pxz, const double *zp, const double *S, const double *z,
+                       double *x, double *P, double *K, int32_t *status, hipStream_t s)
 {
-    if (n < 1 || n > 16 || m < 1 || m > 8) return fail(FK_ERR_UNSUPPORTED, "ukf correct: dim_x 1..16, dim_z 1..8");
-    if (N < 0 || !Pxz || !S || !z || !x || !P) return fail(FK_ERR_BAD_ARG, "ukf correct: bad argument");
-    if ((double)N * n * n * 8.0 >= 4294967296.0) return fail(FK_ERR_UNSUPPORTED, "ukf correct: record block >= 4 GiB, split the batch");
-    if (N == 0) return FK_OK;
     const dim3 grid((unsigned)((N + BLOCK - 1) / BLOCK)), block(BLOCK);
-    hipStream_t s = (hipStream_t)stream;
-#define GOZ(NXV, NZV)                                                                                      \
-    if (layout == FK_LAYOUT_SOA)                                                                           \
-        hipLaunchKernelGGL((ukf_correct_kernel<NXV, NZV, LAYOUT_SOA>), grid, block, 0, s, n, m, N, Pxz, zp, \
-                           S, z, x, P, K, status);                                                         \
-    else                                                                                                   \
-        hipLaunchKernelGGL((ukf_correct_kernel<NXV, NZV, LAYOUT_AOS>), grid, block, 0, s, n, m, N, Pxz, zp, \
-                           S, z, x, P, K, status)
+#define GOZ(NXV, NZV)                                                                                                      \
+    if (layout == FK_LAYOUT_SOA)                                                                                           \
+        hipLaunchKernelGGL((ukf_correct_kernel<NXV, NZV, LAYOUT_SOA>), grid, block, 0, s, n, m, N, Pxz, zp, S, z, x, P, K, status); \
+    else                                                                                                                   \
+        hipLaunchKernelGGL((ukf_correct_kernel<NXV, NZV, LAYOUT_AOS>), grid, block, 0, s, n, m, N, Pxz, zp, S, z, x, P, K, status)
 #define CALL(NXV)                  \
     if (m <= 4) { GOZ(NXV, 4); }   \
     else { GOZ(NXV, 8); }
@@ -515,6 +470,6 @@ int fk_ukf_correct_f64(int32_t n, int32_t m, int64_t N, int32_t layout, const do
 #undef GOZ
     return check_launch("ukf_correct_kernel");
 }
-
 #endif   // FK_UT_PART
-}  // extern "C"
+
+}  // namespace fk

@@ -6,7 +6,10 @@ fields a family allows, the smoother's k0 and its narrower record -- is what the
 
 The second half does the same for the entry points of the Kalman filter and the IMM estimator (csrc/kf_dispatch.cpp,
 csrc/imm_dispatch.cpp, on the same scaffold): their refusals in the order the code makes them, and -- on machines without a
-device only -- which kernel family a call that passes every check reaches."""
+device only -- which kernel family a call that passes every check reaches.
+
+The third part holds the unscented filter's entry points (csrc/ukf_dispatch.cpp) and the steady-state / correlated-noise
+variants of the Kalman filter: eleven calls with rules of their own, oddities included."""
 import ctypes
 
 import pytest
@@ -714,3 +717,413 @@ def test_imm_reaches_family(env):
         else:                                           # the plain entry point is the extended one without the extras
             assert _family(*_imm("fk_imm_batch_f64", d, only=only)) == family, d
             assert _family(*_imm("fk_imm_batch_ex_f64", d, null=("zmask", "ll0", "B", "u"), only=only)) == family, d
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The unscented filter's entry points (csrc/ukf_dispatch.cpp) and the two Kalman filter variants that moved into
+# csrc/kf_dispatch.cpp with them.  Their rules differ from the descriptor families above and from each other; every oddity
+# below is what callers get (docs/MEASUREMENTS.md lists them as candidates for a bug-fix change) and is pinned as it is.
+
+PAIR = 1                           # FK_UKF_FLAG_PAIR_WEIGHTS
+# entry point -> (what precedes the pointers: "ukf" / "kf" descriptor, or the scalars of a valid small call in order;
+#                 pointers after it, stream last; indices of the required ones; the words its messages start with)
+U_ENTRY = {
+    "fk_ukf_linear_batch_f64": ("ukf", 14, (0, 1, 2, 3, 4, 5, 6, 8, 9), "fused linear UKF"),
+    "fk_ukf_linear_rts_f64": ("ukf", 11, (0, 1, 2, 3, 4, 5, 6, 7), "fused linear UKF smoother"),
+    "fk_ut_sigma_points_f64": (dict(n=2, N=4, layout=0, scale=3.0), 5, (0, 1, 2), "sigma points"),
+    "fk_ut_transform_f64": (dict(n=2, k=5, N=4, layout=0), 7, (0, 1, 2, 4, 5), "unscented transform"),
+    "fk_ut_cross_variance_f64": (dict(n=2, m=1, k=5, N=4, layout=0), 7, (2, 3, 4, 5), "cross variance"),
+    "fk_ut_linear_map_f64": (dict(n_in=2, n_out=1, k=5, N=4, layout=0), 4, (0, 1, 2), "linear map"),
+    "fk_ukf_correct_f64": (dict(n=2, m=1, N=4, layout=0), 9, (0, 2, 3, 4, 5), "ukf correct"),
+    "fk_ukf_rts_correct_f64": (dict(n=2, N=4, layout=0), 10, (0, 2, 3, 4, 5, 6), "ukf rts"),
+    "fk_kf_steadystate_f64": ("kf", 12, (7,), "steady state"),
+    "fk_kf_update_correlated_f64": ("kf", 13, (0, 1, 2, 3, 5, 6), "update_correlated"),
+}
+U_BLOCKS = sorted(n for n in U_ENTRY if isinstance(U_ENTRY[n][0], dict))          # the building blocks: scalar arguments
+U_FUSED = ("fk_ukf_linear_batch_f64", "fk_ukf_linear_rts_f64")
+U_VARIANTS = ("fk_kf_steadystate_f64", "fk_kf_update_correlated_f64")
+# the range refusal of each building block (FK_ERR_UNSUPPORTED, also below 1) and the wrong values that draw it
+U_RANGE = {
+    "fk_ut_sigma_points_f64": ("sigma points: dim_x must be 1..16", [dict(n=0), dict(n=17)]),
+    "fk_ut_transform_f64": ("unscented transform: dim must be 1..16", [dict(n=0), dict(n=17), dict(k=0)]),
+    "fk_ut_cross_variance_f64": ("cross variance: dim_x must be 1..16", [dict(n=0), dict(n=17), dict(m=0), dict(k=0)]),
+    "fk_ut_linear_map_f64": ("linear map: dims must be 1..16", [dict(n_in=0), dict(n_in=17), dict(n_out=0), dict(n_out=17), dict(k=0)]),
+    "fk_ukf_correct_f64": ("ukf correct: dim_x 1..16, dim_z 1..8", [dict(n=0), dict(n=17), dict(m=0), dict(m=9)]),
+    "fk_ukf_rts_correct_f64": ("ukf rts: dim_x 1..16", [dict(n=0), dict(n=17)]),
+}
+# the first track count each building block's record-block guard refuses: exactly 4 GiB, not 32 bytes short of it
+U_FIRST = {
+    "fk_ut_sigma_points_f64": (dict(n=1), 178956971),                  # 3 doubles per track: 2^32 / 24 rounded up
+    "fk_ut_transform_f64": (dict(n=1, k=3), 178956971),
+    "fk_ut_cross_variance_f64": (dict(n=1, m=3, k=1), 178956971),      # k * max(n, m)
+    "fk_ut_linear_map_f64": (dict(n_in=1, n_out=3, k=1), 178956971),
+    "fk_ukf_correct_f64": (dict(n=1, m=8), 2 ** 29),                   # n * n alone: the m x m and n x m records are not counted
+    "fk_ukf_rts_correct_f64": (dict(n=1), 2 ** 29),
+}
+UKF_PAIR_FWD = ("fused linear UKF at dim_x 10..16: needs weights equal within every +- pair (FK_UKF_FLAG_PAIR_WEIGHTS; and "
+                "FK_UKF_MLG != 0)")
+UKF_PAIR_RTS = ("fused linear UKF smoother at dim_x 10..16: needs weights equal within every +- pair (FK_UKF_FLAG_PAIR_WEIGHTS; "
+                "and FK_UKF_MLG != 0)")
+UKF_DIMS_FWD = "fused linear UKF: dim_x 1..6 with dim_z 1..3, dim_x 7..9 with dim_z 1..4, dim_x 10..16 with dim_z 1..8"
+UKF_DIMS_RTS = "fused linear UKF smoother: dim_x 1..9, 10..16"
+# every environment variable these entry points and their launchers read
+U_SWITCHES = ("FK_UKF_MLG", "FK_UKF_MLG_MIN_NX", "FK_UKF_MLG_RTS_MIN_NX", "FK_UKF_MLG_LANES", "FK_UKF_MLG_RTS_LANES", "FK_UKF_PADDED",
+              "FK_UKF_PAIRED", "FK_UKF_DMA", "FK_UKF_SOA_PAIRS", "FK_UKF_CHUNKS", "FK_UKF_RTS_CHUNKS", "FK_UKF_PERSIST",
+              "FK_UKF_PERSIST_H", "FK_UT_COOP", "FK_STEADY_ROLLED", "FK_STEADY_AOS_WAVES")
+
+
+@pytest.fixture
+def uenv(monkeypatch):
+    for v in U_SWITCHES:
+        monkeypatch.delenv(v, raising=False)
+    return monkeypatch
+
+
+def _u(name, over=None, null=(), all_null=False, no_desc=False):
+    """One call with fake pointers; returns (code, last error).  over: the leading arguments that differ from a valid small
+    call."""
+    from filterpy_amd import _abi
+    lib = _abi.lib()
+    head, nptr = U_ENTRY[name][:2]
+    over = dict(over or {})
+    if head == "ukf":
+        fields = dict(n=2, m=1, N=4, T=3, layout=_abi.FK_LAYOUT_AOS, flags=0, scale=3.0)
+        fields.update(over)
+        d = _abi.fk_ukf_desc(**fields)
+        lead = [None if no_desc else ctypes.byref(d)]
+    elif head == "kf":
+        fields = dict(n=2, m=1, nu=0, model_mode=_abi.FK_MODEL_SHARED, N=4, T=3, layout=_abi.FK_LAYOUT_AOS, update_first=0,
+                      alpha_sq=1.0, flags=0)
+        fields.update(over)
+        d = _abi.fk_kf_desc(**fields)
+        lead = [None if no_desc else ctypes.byref(d)]
+    else:
+        assert set(over) <= set(head), over
+        lead = [over.get(k, v) for k, v in head.items()]
+    ptrs = [None if (all_null or i in null) else ONE for i in range(nptr)]
+    ptrs[-1] = None                                                            # stream
+    rc = getattr(lib, name)(*lead, *ptrs)
+    return rc, lib.fk_last_error().decode()
+
+
+def _bad(name):
+    return U_ENTRY[name][3] + ": bad argument"
+
+
+def _guard(name):
+    return U_ENTRY[name][3] + ": record block >= 4 GiB" + ("" if name in U_VARIANTS + ("fk_ukf_rts_correct_f64",) else ", split the batch")
+
+
+@pytest.mark.parametrize("name", U_FUSED + U_VARIANTS)
+def test_u_null_desc(name, uenv):
+    assert _u(name, no_desc=True) == (BAD_ARG, "desc is NULL")
+    assert _u(name, no_desc=True, all_null=True) == (BAD_ARG, "desc is NULL")
+
+
+def test_ukf_linear_supported_is_the_table_of_the_fused_calls(uenv):
+    """No descriptor, no message: 1 where the fused call takes the size.  Sizes whose answer does not depend on the
+    FK_UKF_MLG* switches (tests/test_host_logic.py gives those an interpreter each)."""
+    from filterpy_amd import _abi
+    q = _abi.lib().fk_ukf_linear_supported
+    for flags in (0, PAIR, 2, PAIR | 2):
+        for n in range(-1, 19):
+            for m in range(-1, 11):
+                small = (1 <= n <= 6 and 1 <= m <= 3) or (7 <= n <= 9 and 1 <= m <= 4)
+                if not 10 <= n <= 16:
+                    assert q(n, m, flags, 0) == int(small), (n, m, flags)
+                    assert q(n, m, flags, 1) == int(1 <= n <= 9), (n, m, flags)            # the smoother does not read dim_z
+                elif not flags & PAIR:
+                    assert q(n, m, flags, 0) == 0 and q(n, m, flags, 1) == 0, (n, m, flags)
+                elif not 1 <= m <= 8:
+                    assert q(n, m, flags, 0) == 0, (n, m, flags)
+    assert q(6, 3, 0, 7) == 1 and q(6, 4, 0, -1) == 1                                      # smoother: any nonzero value
+
+
+def test_ukf_fused_refusals_in_order(uenv):
+    fwd, rts = U_FUSED
+    # the sizes: FK_ERR_UNSUPPORTED also below 1, and before anything else is looked at
+    for over in (dict(n=0), dict(n=-1), dict(n=17), dict(m=0), dict(m=5), dict(n=6, m=4), dict(n=9, m=5), dict(n=10, m=9),
+                 dict(n=16, m=0), dict(n=12, m=9, flags=PAIR)):
+        assert _u(fwd, dict(over, N=-1), all_null=True) == (UNSUPPORTED, UKF_DIMS_FWD), over
+    for over in (dict(n=0), dict(n=-1), dict(n=17), dict(n=17, flags=PAIR)):
+        assert _u(rts, dict(over, N=-1), all_null=True) == (UNSUPPORTED, UKF_DIMS_RTS), over
+    assert _u(rts, dict(n=9, m=0), null=(0,)) == (BAD_ARG, _bad(rts))                       # the smoother does not read dim_z
+    # dim_x 10..16 without the pair-weight flag (any other bit does not count)
+    for n in (10, 13, 16):
+        for flags in (0, 2):
+            assert _u(fwd, dict(n=n, m=8, flags=flags, T=-1), all_null=True) == (UNSUPPORTED, UKF_PAIR_FWD)
+            assert _u(rts, dict(n=n, m=9, flags=flags, T=-1), all_null=True) == (UNSUPPORTED, UKF_PAIR_RTS)
+    # N < 0, T < 0 and a missing pointer are one refusal, "bad argument"
+    for name in U_FUSED:
+        assert _u(name, dict(N=-1)) == (BAD_ARG, _bad(name))
+        assert _u(name, dict(T=-1)) == (BAD_ARG, _bad(name))
+        for i in U_ENTRY[name][2]:
+            assert _u(name, null=(i,)) == (BAD_ARG, _bad(name)), (name, i)
+        # layout is not looked at: with nothing to do any value is FK_OK
+        for layout in (0, 1, 2, -1):
+            assert _u(name, dict(layout=layout, N=0))[0] == 0
+            assert _u(name, dict(layout=layout, T=0))[0] == 0
+        # nothing to do is answered after the pointers, not before: an empty bank with NULL pointers is a bad argument
+        assert _u(name, dict(N=0), all_null=True) == (BAD_ARG, _bad(name))
+        assert _u(name, dict(T=0), all_null=True) == (BAD_ARG, _bad(name))
+        optional = [i for i in range(U_ENTRY[name][1]) if i not in U_ENTRY[name][2]]
+        assert _u(name, dict(N=0), null=optional)[0] == 0
+        assert _u(name, dict(T=0), null=optional)[0] == 0
+
+
+def test_ukf_fused_record_block_guards(uenv):
+    """N * dim_x^2 * 8 bytes: the forward call refuses 32 bytes short of 4 GiB, the one-lane smoother at 4 GiB exactly; both
+    after the pointers and before "nothing to do"."""
+    fwd, rts = U_FUSED
+    assert _u(fwd, dict(n=1, N=2 ** 29 - 4)) == (UNSUPPORTED, _guard(fwd))
+    assert _u(fwd, dict(n=1, N=2 ** 29 - 4, T=0)) == (UNSUPPORTED, _guard(fwd))
+    assert _u(fwd, dict(n=1, N=2 ** 29 - 5, T=0))[0] == 0
+    assert _u(fwd, dict(n=6, m=3, N=14913081, T=0)) == (UNSUPPORTED, _guard(fwd))          # 288 bytes per track
+    assert _u(fwd, dict(n=6, m=3, N=14913080, T=0))[0] == 0
+    assert _u(fwd, dict(n=1, N=2 ** 29), null=(0,)) == (BAD_ARG, _bad(fwd))
+    for flags in (0, PAIR):                                                                # dim_x 1 is never on several lanes
+        assert _u(rts, dict(n=1, N=2 ** 29, flags=flags)) == (UNSUPPORTED, _guard(rts))
+        assert _u(rts, dict(n=1, N=2 ** 29, T=0, flags=flags)) == (UNSUPPORTED, _guard(rts))
+        assert _u(rts, dict(n=1, N=2 ** 29 - 1, T=0, flags=flags))[0] == 0
+        assert _u(rts, dict(n=1, N=2 ** 29, flags=flags), null=(7,)) == (BAD_ARG, _bad(rts))
+    assert _u(rts, dict(n=6, N=14913081, T=0)) == (UNSUPPORTED, _guard(rts))
+    assert _u(rts, dict(n=6, N=14913080, T=0))[0] == 0
+
+
+@pytest.mark.parametrize("name", U_BLOCKS)
+def test_ut_block_refusals_in_order(name, uenv):
+    """range (FK_ERR_UNSUPPORTED) -> [layout: fk_ukf_rts_correct_f64 only] -> N < 0 or a missing pointer ("bad argument") ->
+    the 4 GiB guard -> nothing to do."""
+    lead, nptr, required, _ = U_ENTRY[name]
+    range_msg, wrong = U_RANGE[name]
+    for over in wrong:
+        assert _u(name, dict(over, N=-1, layout=2), all_null=True) == (UNSUPPORTED, range_msg), over
+    if name == "fk_ukf_rts_correct_f64":
+        for layout in (2, -1):
+            assert _u(name, dict(layout=layout, N=-1), all_null=True) == (BAD_ARG, "ukf rts: bad layout")
+    else:       # layout is not checked: whatever is not FK_LAYOUT_SOA runs the NumPy-order kernel
+        for layout in (2, -1):
+            assert _u(name, dict(layout=layout, N=0))[0] == 0
+    assert _u(name, dict(N=-1)) == (BAD_ARG, _bad(name))
+    for i in required:
+        assert _u(name, null=(i,)) == (BAD_ARG, _bad(name)), i
+    shape, first = U_FIRST[name]
+    assert _u(name, dict(shape, N=first)) == (UNSUPPORTED, _guard(name))
+    assert _u(name, dict(shape, N=2 ** 40)) == (UNSUPPORTED, _guard(name))
+    assert _u(name, dict(shape, N=first), null=required[:1]) == (BAD_ARG, _bad(name))       # the pointers come first
+    # nothing to do: FK_OK once the required pointers are there -- with every pointer NULL an empty bank is a bad argument
+    optional = [i for i in range(nptr) if i not in required]
+    assert _u(name, dict(N=0), null=optional)[0] == 0
+    assert _u(name, dict(N=0), all_null=True) == (BAD_ARG, _bad(name))
+
+
+def test_ut_block_oddities(uenv):
+    # the transform reports k < 1 in the words of a dimension; cross variance has no upper bound on dim_z and k, and does not
+    # ask for x and z (NULL: the caller applied its own residuals); the correction's zp, K and status are optional
+    assert _u("fk_ut_transform_f64", dict(k=0)) == (UNSUPPORTED, "unscented transform: dim must be 1..16")
+    assert _u("fk_ut_transform_f64", dict(k=-3, n=17)) == (UNSUPPORTED, "unscented transform: dim must be 1..16")
+    assert _u("fk_ut_cross_variance_f64", dict(m=9, k=99, N=0))[0] == 0
+    assert _u("fk_ut_cross_variance_f64", dict(N=0), null=(0, 1))[0] == 0
+    assert _u("fk_ut_linear_map_f64", dict(k=99, N=0))[0] == 0
+    assert _u("fk_ukf_correct_f64", dict(N=0), null=(1, 6, 7))[0] == 0
+    assert _u("fk_ukf_rts_correct_f64", dict(N=0), null=(1, 7, 8))[0] == 0
+
+
+@pytest.mark.parametrize("name", U_VARIANTS)
+def test_kf_variant_refusals_in_order(name, uenv):
+    """desc -> sizes (FK_ERR_UNSUPPORTED, also below 1) -> layout -> model mode -> "bad argument" -> the 4 GiB guard ->
+    nothing to do."""
+    words, steady = U_ENTRY[name][3], name == "fk_kf_steadystate_f64"
+    sizes = words + (": dim_x 1..16, dim_z 1..8, dim_u 0..4" if steady else ": dim_x 1..16, dim_z 1..8")
+    for over in (dict(n=0), dict(n=17), dict(m=0), dict(m=9)) + ((dict(nu=-1), dict(nu=5)) if steady else ()):
+        assert _u(name, dict(over, layout=2, model_mode=2, N=-1), all_null=True) == (UNSUPPORTED, sizes), over
+    if not steady:                                               # update_correlated does not read dim_u
+        assert _u(name, dict(nu=-1, N=0))[0] == 0 and _u(name, dict(nu=5, N=0))[0] == 0
+    for layout in (2, -1):
+        assert _u(name, dict(layout=layout, model_mode=2, N=-1), all_null=True) == (BAD_ARG, words + ": bad layout")
+    mode = words + (": K is shared or per track" if steady else ": M is shared or per track")
+    for m in (2, 3, -1, 4):
+        assert _u(name, dict(model_mode=m, N=-1), all_null=True) == (UNSUPPORTED, mode)
+    assert _u(name, dict(model_mode=1, N=0))[0] == 0
+    assert _u(name, dict(N=-1)) == (BAD_ARG, _bad(name))
+    for i in U_ENTRY[name][2]:
+        assert _u(name, null=(i,)) == (BAD_ARG, _bad(name)), i
+    # the guard: N * dim_x * dim_z (steady state) / N * dim_x^2 (update_correlated) * 8 bytes, 4 GiB exactly, after the pointers
+    first = 2 ** 28 if steady else 2 ** 27
+    assert _u(name, dict(N=first)) == (UNSUPPORTED, _guard(name))
+    assert _u(name, dict(N=first), null=U_ENTRY[name][2][:1]) == (BAD_ARG, _bad(name))
+    # nothing to do, after the pointers; alpha_sq, update_first and flags are not read
+    assert _u(name, dict(N=0, alpha_sq=2.0, update_first=1, flags=255))[0] == 0
+    assert _u(name, dict(N=0), all_null=True) == (BAD_ARG, _bad(name))
+    if steady:
+        assert _u(name, dict(T=-1)) == (BAD_ARG, _bad(name))
+        assert _u(name, dict(T=0))[0] == 0
+        assert _u(name, dict(T=0, N=first)) == (UNSUPPORTED, _guard(name))
+    else:                                                        # one step: T is not read
+        assert _u(name, dict(T=-1, N=0))[0] == 0
+        assert _u(name, dict(T=0), null=(0,)) == (BAD_ARG, _bad(name))
+
+
+def test_kf_steadystate_argument_rule(uenv):
+    """F H K B u z mask x means means_p y_out: x always; F (predict) or z (update) or both; an update needs H and K; a
+    predict with dim_u > 0 needs B and u."""
+    name = "fk_kf_steadystate_f64"
+    F, H, K, B, U, Z = 0, 1, 2, 3, 4, 5
+    bad = (BAD_ARG, _bad(name))
+    assert _u(name, dict(N=0), null=(F, Z)) == bad
+    assert _u(name, dict(N=0), null=(H,)) == bad
+    assert _u(name, dict(N=0), null=(K,)) == bad
+    assert _u(name, dict(N=0, nu=1), null=(B,)) == bad
+    assert _u(name, dict(N=0, nu=4), null=(U,)) == bad
+    assert _u(name, dict(N=0), null=(F, B, U, 6, 8, 9, 10))[0] == 0                         # update alone
+    assert _u(name, dict(N=0, nu=2), null=(F, B, U))[0] == 0                               # ... needs no control input
+    assert _u(name, dict(N=0), null=(Z, H, K, B, U))[0] == 0                               # predict alone
+    assert _u(name, dict(N=0, nu=2), null=(Z, H, K))[0] == 0
+
+
+# Which kernel family a valid call reaches, on device-less machines (see above).  The routing switches of these entry points
+# are read once per process, so every setting walks its table in an interpreter of its own.
+
+def _route_call(name, over, null=()):
+    return list(_u(name, over, null=null))
+
+
+def _walk(calls, switches):
+    """[(name, over, null)] -> [(code, family or message)] from a fresh interpreter with only `switches` set."""
+    import json
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = ("import json, sys; sys.path[:0] = [%r, %r]; import test_host_refusals as t; "
+            "print(json.dumps([t._route_call(*c) for c in json.load(sys.stdin)]))" % (os.path.dirname(here), here))
+    e = {k: v for k, v in os.environ.items() if k not in U_SWITCHES}
+    e.update(switches)
+    out = subprocess.run([sys.executable, "-c", code], input=json.dumps(calls), capture_output=True, text=True, env=e, check=True)
+    return [(rc, msg.split(":")[0] if rc == LAUNCH else msg if rc else "") for rc, msg in json.loads(out.stdout.splitlines()[-1])]
+
+
+def _no_device():
+    import torch
+    return not torch.cuda.is_available()
+
+
+FWD, RTS = "ukf_linear_kernel", "ukf_linear_rts_kernel"
+QUAD, OCT = "ukf_mlg_kernel", "ukf_mlg_kernel<8 lanes>"
+RQUAD, ROCT = "ukf_mlg_rts_kernel", "ukf_mlg_rts_kernel<8 lanes>"
+NO_F, NO_R, PAIR_F, PAIR_R = (UKF_DIMS_FWD,) * 2, (UKF_DIMS_RTS,) * 2, (UKF_PAIR_FWD,) * 2, (UKF_PAIR_RTS,) * 2
+# the first N with N * dim_x^2 * 8 >= 4 GiB, for the smoother's guards on its two routes
+RTS_FIRST = {7: 10956550, 9: 6628036, 10: 5368710, 16: 2 ** 21}
+_BAD, _GUARD = (BAD_ARG, "fused linear UKF smoother: bad argument"), (UNSUPPORTED, "fused linear UKF smoother: record block >= 4 GiB, split the batch")
+_PAIR, _OK = (UNSUPPORTED, UKF_PAIR_RTS), (0, "")
+# Per setting of the switches (one interpreter each; switches that do not meet share one):
+#   fwd:    (dim_x, dim_z) -> what the fused forward call reaches (without, with the pair-weight flag), both layouts alike
+#   rts:    dim_x -> the same for the fused smoother
+#   guards: the smoother at RTS_FIRST[dim_x] tracks with F NULL, dim_x 7, 9, 10, 16 x (without, with the flag) -- where it runs
+#           on several lanes per track the guard sits in front of the pointer checks (and 32 bytes short of 4 GiB; no
+#           N * dim_x^2 * 8 falls into those 32 bytes for dim_x >= 7), on the one-lane route behind them --, then the four sizes one
+#           track below with the flag, every pointer there and T = 0
+UKF_ROUTES = {
+    "": dict(
+        fwd={(6, 3): (FWD, FWD), (6, 4): NO_F, (7, 4): (FWD, FWD), (9, 4): (FWD, FWD), (9, 5): NO_F, (10, 1): (UKF_PAIR_FWD, QUAD),
+             (12, 8): (UKF_PAIR_FWD, QUAD), (13, 4): (UKF_PAIR_FWD, QUAD), (13, 5): (UKF_PAIR_FWD, OCT), (16, 8): (UKF_PAIR_FWD, OCT),
+             (17, 1): NO_F},
+        rts={6: (RTS, RTS), 7: (RTS, RQUAD), 9: (RTS, RQUAD), 10: (UKF_PAIR_RTS, RQUAD), 12: (UKF_PAIR_RTS, RQUAD),
+             13: (UKF_PAIR_RTS, ROCT), 16: (UKF_PAIR_RTS, ROCT), 17: NO_R},
+        guards=[_BAD, _GUARD, _BAD, _GUARD, _PAIR, _GUARD, _PAIR, _GUARD] + [_OK] * 4),
+    "FK_UKF_MLG=0": dict(
+        fwd={(6, 3): (FWD, FWD), (9, 4): (FWD, FWD), (10, 1): PAIR_F, (16, 8): PAIR_F, (16, 9): NO_F},
+        rts={6: (RTS, RTS), 7: (RTS, RTS), 9: (RTS, RTS), 10: PAIR_R, 16: PAIR_R, 17: NO_R},
+        guards=[_BAD] * 4 + [_PAIR] * 4 + [_OK, _OK, _PAIR, _PAIR]),
+    "FK_UKF_MLG_MIN_NX=7 FK_UKF_MLG_RTS_MIN_NX=10 FK_UT_COOP=0 FK_STEADY_ROLLED=1": dict(
+        fwd={(6, 3): (FWD, FWD), (7, 4): (FWD, QUAD), (9, 4): (FWD, QUAD), (9, 5): NO_F, (10, 1): (UKF_PAIR_FWD, QUAD)},
+        rts={7: (RTS, RTS), 9: (RTS, RTS), 10: (UKF_PAIR_RTS, RQUAD)},
+        guards=[_BAD] * 4 + [_PAIR, _GUARD, _PAIR, _GUARD] + [_OK] * 4),
+    "FK_UKF_MLG_MIN_NX=9 FK_UKF_MLG_RTS_MIN_NX=9 FK_UKF_PADDED=1 FK_UKF_DMA=0 FK_UT_COOP=1 FK_STEADY_AOS_WAVES=3": dict(
+        fwd={(6, 3): (FWD, FWD), (7, 4): (FWD, FWD), (9, 4): (FWD, QUAD), (10, 1): (UKF_PAIR_FWD, QUAD)},
+        rts={6: (RTS, RTS), 7: (RTS, RTS), 9: (RTS, RQUAD)},
+        guards=[_BAD, _BAD, _BAD, _GUARD, _PAIR, _GUARD, _PAIR, _GUARD] + [_OK] * 4),
+    "FK_UKF_MLG_MIN_NX=7 FK_UKF_PAIRED=0 FK_STEADY_AOS_WAVES=1": dict(
+        fwd={(6, 3): (FWD, FWD), (7, 4): (FWD, FWD), (9, 4): (FWD, FWD), (10, 1): (UKF_PAIR_FWD, QUAD), (16, 8): (UKF_PAIR_FWD, OCT)},
+        rts={6: (RTS, RTS), 7: (RTS, RTS), 9: (RTS, RTS), 10: (UKF_PAIR_RTS, RQUAD)},
+        guards=[_BAD] * 4 + [_PAIR, _GUARD, _PAIR, _GUARD] + [_OK] * 4),
+    "FK_UKF_MLG_LANES=4 FK_UKF_MLG_RTS_LANES=4": dict(
+        fwd={(13, 5): (UKF_PAIR_FWD, QUAD), (16, 8): (UKF_PAIR_FWD, QUAD)},
+        rts={9: (RTS, RQUAD), 16: (UKF_PAIR_RTS, RQUAD)},
+        guards=[_BAD, _GUARD, _BAD, _GUARD, _PAIR, _GUARD, _PAIR, _GUARD] + [_OK] * 4),
+    "FK_UKF_MLG_LANES=8 FK_UKF_MLG_RTS_LANES=8": dict(
+        fwd={(9, 4): (FWD, FWD), (10, 1): (UKF_PAIR_FWD, OCT)},
+        rts={7: (RTS, RQUAD), 9: (RTS, ROCT), 10: (UKF_PAIR_RTS, ROCT)},
+        guards=[_BAD, _GUARD, _BAD, _GUARD, _PAIR, _GUARD, _PAIR, _GUARD] + [_OK] * 4),
+}
+
+
+def _block_routes(coop):
+    """The building blocks and the two variants: (entry point, leading arguments, family).  coop: FK_UT_COOP is not 0."""
+    r = []
+    for layout in (0, 1, 2):            # 2: not a layout; whatever is not element-major runs the NumPy-order kernel
+        for n in (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 13, 16):
+            tile = coop and layout == 0 and n in (2, 4, 6)
+            r.append(("fk_ut_sigma_points_f64", dict(n=n, N=300, layout=layout), "sigma_coop_kernel" if tile else "sigma_kernel"))
+            for k in (2 * n + 1, 2 * n, 1):
+                standard = k == 2 * n + 1 and n in (2, 4, 6)
+                family = "ut_coop_kernel" if tile and standard else "ut_reg_kernel" if standard else "ut_kernel"
+                r.append(("fk_ut_transform_f64", dict(n=n, k=k, N=300, layout=layout), family))
+            for m in (1, 4, 5, 8):
+                r.append(("fk_ut_cross_variance_f64", dict(n=n, m=m, k=2 * n + 1, N=300, layout=layout), "cross_kernel"))
+                r.append(("fk_ut_linear_map_f64", dict(n_in=n, n_out=m, k=2 * n + 1, N=300, layout=layout), "linear_map_kernel"))
+                r.append(("fk_ut_linear_map_f64", dict(n_in=m, n_out=n, k=2 * n, N=300, layout=layout), "linear_map_kernel"))
+                r.append(("fk_ukf_correct_f64", dict(n=n, m=m, N=300, layout=layout), "ukf_correct_kernel"))
+            if layout < 2:
+                r.append(("fk_ukf_rts_correct_f64", dict(n=n, N=300, layout=layout), "ukf_rts_kernel"))
+    for layout in (0, 1):
+        for n, m in ((2, 1), (2, 2), (4, 2), (6, 3), (6, 4), (9, 3), (9, 4), (10, 4), (9, 5), (12, 8), (13, 1), (16, 8)):
+            for mode in (0, 1):
+                r.append(("fk_kf_steadystate_f64", dict(n=n, m=m, N=300, layout=layout, model_mode=mode), "steady_kernel"))
+                r.append(("fk_kf_steadystate_f64", dict(n=n, m=m, nu=2, N=300, layout=layout, model_mode=mode), "steady_kernel"))
+                r.append(("fk_kf_update_correlated_f64", dict(n=n, m=m, N=300, layout=layout, model_mode=mode), "corr_update_kernel"))
+    # one track below the first count a guard refuses the call reaches its launch: the building blocks' guards sit at 4 GiB
+    # exactly (at 3 doubles per track that block ends 16 bytes short of 4 GiB, which a guard 32 bytes short would refuse)
+    r += [(name, dict(U_FIRST[name][0], N=U_FIRST[name][1] - 1), None) for name in U_BLOCKS]
+    r += [("fk_kf_steadystate_f64", dict(N=2 ** 28 - 1), None), ("fk_kf_update_correlated_f64", dict(N=2 ** 27 - 1), None)]
+    return r
+
+
+@pytest.mark.parametrize("switches", sorted(UKF_ROUTES))
+def test_ukf_and_variants_reach_family(switches):
+    if not _no_device():
+        return
+    fwd, rts, blocks = "fk_ukf_linear_batch_f64", "fk_ukf_linear_rts_f64", _block_routes("FK_UT_COOP=0" not in switches)
+    t = UKF_ROUTES[switches]
+    kf = [(nm, layout, flags) for nm in sorted(t["fwd"]) for layout in (0, 1) for flags in (0, PAIR)]
+    kr = [(n, layout, flags, gains) for n in sorted(t["rts"]) for layout in (0, 1) for flags in (0, PAIR) for gains in (True, False)]
+    calls = [(fwd, dict(n=n, m=m, N=300, layout=layout, flags=flags)) for (n, m), layout, flags in kf]
+    calls += [(rts, dict(n=n, N=300, layout=layout, flags=flags), () if gains else (8, 9)) for n, layout, flags, gains in kr]
+    calls += [(rts, dict(n=n, N=N, flags=flags), (0,)) for n, N in sorted(RTS_FIRST.items()) for flags in (0, PAIR)]
+    calls += [(rts, dict(n=n, N=N - 1, flags=PAIR, T=0)) for n, N in sorted(RTS_FIRST.items())]
+    calls += [(name, over) for name, over, _ in blocks]
+    got = _walk(calls, dict(s.split("=") for s in switches.split()))
+    code = lambda family: (UNSUPPORTED if family.startswith("fused") else LAUNCH, family)         # noqa: E731
+    want = [code(t["fwd"][nm][flags]) for nm, layout, flags in kf] + [code(t["rts"][n][flags]) for n, layout, flags, gains in kr]
+    want += t["guards"]
+    want += [(LAUNCH, family) for _, _, family in blocks]
+    got = [(rc, w[1] if w[1] is None else msg) for (rc, msg), w in zip(got, want)]               # (None: any family)
+    assert got == want, [(c, g, w) for c, g, w in zip(calls, got, want) if g != w]
+
+
+def test_ukf_chunked_calls_without_a_device(uenv):
+    """FK_UKF_CHUNKS / FK_UKF_RTS_CHUNKS are read per call.  Without a device there are no helper streams: the call is one
+    launch, which fails like any other."""
+    if not _no_device():
+        return
+    for chunks in ("2,2", "4,3", "1,1", "nonsense"):
+        uenv.setenv("FK_UKF_CHUNKS", chunks)
+        uenv.setenv("FK_UKF_RTS_CHUNKS", chunks)
+        for layout in (0, 1):
+            rc, msg = _u("fk_ukf_linear_batch_f64", dict(n=6, m=3, N=2048, T=8, layout=layout))
+            assert (rc, msg.split(":")[0]) == (LAUNCH, FWD), chunks
+            rc, msg = _u("fk_ukf_linear_rts_f64", dict(n=6, N=2048, T=8, layout=layout))
+            assert (rc, msg.split(":")[0]) == (LAUNCH, RTS), chunks
+    uenv.delenv("FK_UKF_RTS_CHUNKS")
+    rc, msg = _u("fk_ukf_linear_rts_f64", dict(n=6, N=100000, T=100))       # the default policy's shape: 1563 waves, 1024 slots
+    assert (rc, msg.split(":")[0]) == (LAUNCH, RTS)

@@ -32,7 +32,7 @@ def main():
     if a.kind == "fwd":
         nx, nz = int(a.dims[0]), int(a.dims[1])
         inst = (f"template __global__ void fk::ukf_linear_kernel<{nx}, {nz}, {lay}, {exact}, {paired}, {'true' if a.sp else 'false'}>(const fk::UkfArgs, const double *, "
-                "const double *, const double *, const double *, const double *, const double *, const double *, const uint8_t *);")
+                "const double *, const double *, const double *, const double *, const double *, const double *, const uint8_t *, int *, double *, int, int);")
         part = 91
     else:
         nx = int(a.dims[0])
