@@ -10,10 +10,16 @@
 // Update, with PHT = P H', S = H PHT + R, K = PHT S^-1 as in the reference:
 //   (I-KH) P          = P - K PHT'                        =: T1   (row i: U(i,:) - K_i PHT')
 //   T1 (I-KH)'        = T1 - (T1 H') K'                           (G_i = T1_i H', m values)
-//   Joseph:  P+ = T1 (I-KH)' + K R K' = T1 + ((K R)_i - G_i) K'   (upper triangle only)
+//   Joseph:  A = T1 (I-KH)' + K R K' = T1 + ((K R)_i - G_i) K'
 // i.e. the reference's (I-KH) P (I-KH)' + K R K' with the identity-minus-product factors applied
 // implicitly; rounding differences vs the factored form are O(eps |P|), the same size as the
-// reference's own.
+// reference's own.  A is symmetric only up to rounding: element (i,j) computed in row i carries
+// the rounding of K_i PHT', element (j,i) that of K_j PHT'.  Keeping ONE triangle (SYMM = false)
+// turns the antisymmetric part of that rounding into an error of the covariance that the next
+// steps carry on -- on ill-conditioned models 6-20 x the error of the reference, which keeps both
+// triangles; P+ = (A + A') / 2 (SYMM = true: row i also forms the elements left of the diagonal
+// and adds its half to what row j < i stored) cancels it: 1.1-2.1 x the reference
+// (docs/KERNEL_NOTES.md, "The packed-symmetric update keeps both triangles' rounding").
 #pragma once
 #include <type_traits>
 
@@ -113,7 +119,8 @@ FK_HD void kf_predict_sym(double (&x)[NX], double (&U)[NX * (NX + 1) / 2], const
 
 // Returns status bits.  K, y, S (full m x m) and the factorisation are outputs like kf_update.
 // UPD_CACHE: a caller whose own register peak sits in the update half switches the H / R copy off (model_cached)
-template <int NX, int NZ, bool FAST_RCP = false, bool UPD_CACHE = true, class Model>
+// SYMM: P+ = (A + A') / 2 instead of A's upper triangle (above); the IMM kernels keep the triangle
+template <int NX, int NZ, bool FAST_RCP = false, bool UPD_CACHE = true, bool SYMM = false, class Model>
 FK_HD int kf_update_sym(double (&x)[NX], double (&U)[NX * (NX + 1) / 2], const double (&z)[NZ], const Model &M,
                         double (&K)[NX * NZ], double (&y)[NZ], double (&S)[NZ * NZ],
                         double (&Lf)[NZ * NZ], double (&dinv)[NZ], bool rj_diag = false)
@@ -197,10 +204,18 @@ FK_HD int kf_update_sym(double (&x)[NX], double (&U)[NX * (NX + 1) / 2], const d
             FK_ROWH(r, h);
             D[r] -= dot<NX>(t1, h);
         }
+        if constexpr (SYMM) {
+            FK_UNROLL for (int j = 0; j < i; ++j) {
+                double acc = t1[j];
+                FK_UNROLL for (int r = 0; r < NZ; ++r) acc = fma(D[r], K[j * NZ + r], acc);
+                Un[sym_idx<NX>(j, i)] = fma(0.5, acc, Un[sym_idx<NX>(j, i)]);
+            }
+            FK_STAGE();
+        }
         FK_UNROLL for (int j = i; j < NX; ++j) {
             double acc = t1[j];
             FK_UNROLL for (int r = 0; r < NZ; ++r) acc = fma(D[r], K[j * NZ + r], acc);
-            Un[sym_idx<NX>(i, j)] = acc;
+            Un[sym_idx<NX>(i, j)] = (SYMM && j > i) ? 0.5 * acc : acc;
         }
         FK_STAGE();
     }

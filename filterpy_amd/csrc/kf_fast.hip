@@ -302,10 +302,10 @@ kf_fast_kernel(const KfArgs a, const double *__restrict__ pF, const double *__re
                 double zq[NZ];
                 FK_UNROLL for (int c = 0; c < NZ; ++c) zq[c] = ZDMA ? zdm[ZDMA ? c : 0] : zu[c];
                 if constexpr (MMODE == 1 || MMODE == 2) {
-                    if constexpr (SYM) st |= kf_update_sym<NX, NZ>(x, P, zq, tm, K, y, S, Lf, dinv);
+                    if constexpr (SYM) st |= kf_update_sym<NX, NZ, false, true, true>(x, P, zq, tm, K, y, S, Lf, dinv);
                     else st |= kf_update<NX, NZ>(x, P, zq, tm, K, y, S, Lf, dinv);
                 } else {
-                    if constexpr (SYM) st |= kf_update_sym<NX, NZ, false, UPDC>(x, P, zq, sm, K, y, S, Lf, dinv);
+                    if constexpr (SYM) st |= kf_update_sym<NX, NZ, false, UPDC, true>(x, P, zq, sm, K, y, S, Lf, dinv);
                     else st |= kf_update<NX, NZ>(x, P, zq, sm, K, y, S, Lf, dinv);
                 }
             }

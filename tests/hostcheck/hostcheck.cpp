@@ -142,7 +142,7 @@ static int kf_batch_sym(long T, const double *F, const double *Q, const double *
         unpackP(covs_p + t * NX * NX);
         if (!mask || mask[t]) {
             double K[NX * NZ], y[NZ], S[NZ * NZ], Lf[NZ * NZ], dinv[NZ];
-            st |= kf_update_sym<NX, NZ>(x, U, zz, M, K, y, S, Lf, dinv);
+            st |= kf_update_sym<NX, NZ, false, true, true>(x, U, zz, M, K, y, S, Lf, dinv);     // as kf_fast.hip calls it
         }
         for (int i = 0; i < NX; ++i) means[t * NX + i] = x[i];
         unpackP(covs + t * NX * NX);
@@ -158,7 +158,7 @@ extern "C" int hc_kf_batch_sym(int n, int m, long T, const double *F, const doub
 {
 #define SYMCALL(NX, NZ) \
     if (n == NX && m == NZ) return kf_batch_sym<NX, NZ>(T, F, Q, H, R, z, mask, x0, P0, means, covs, means_p, covs_p, alpha_sq);
-    SYMCALL(1, 1) SYMCALL(2, 1) SYMCALL(4, 2) SYMCALL(6, 3) SYMCALL(9, 3)
+    SYMCALL(1, 1) SYMCALL(2, 1) SYMCALL(4, 2) SYMCALL(6, 3) SYMCALL(9, 3) SYMCALL(7, 4) SYMCALL(8, 4) SYMCALL(9, 4)
 #undef SYMCALL
     return -1;
 }
