@@ -131,7 +131,8 @@ FK_HD int imm_update(double (&xs)[NM][NX], double (&Ps)[NM][NX * (NX + 1) / 2], 
                     : m == 7 ? 0.0016083125866532416 : m == 8 ? 0.000641623890917771 : 1.0;
     FK_UNROLL for (int j = 0; j < NM; ++j) {
         double K[NX * NZ], y[NZ], S[NZ * NZ], Lf[NZ * NZ], dinv[NZ];
-        st |= kf_update_sym<NX, NZ, true>(xs[j], Ps[j], z, mods[j], K, y, S, Lf, dinv);
+        // (SYMM: both triangles of the Joseph form, fk_math_sym.hpp -- one triangle sat AT the bar of tests/imm_hp.py on stiff banks)
+        st |= kf_update_sym<NX, NZ, true, true, true>(xs[j], Ps[j], z, mods[j], K, y, S, Lf, dinv);
         double q = 0.0;
         if constexpr (NZ == 1) {
             q = y[0] * y[0] * dinv[0];

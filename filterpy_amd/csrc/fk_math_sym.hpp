@@ -119,7 +119,8 @@ FK_HD void kf_predict_sym(double (&x)[NX], double (&U)[NX * (NX + 1) / 2], const
 
 // Returns status bits.  K, y, S (full m x m) and the factorisation are outputs like kf_update.
 // UPD_CACHE: a caller whose own register peak sits in the update half switches the H / R copy off (model_cached)
-// SYMM: P+ = (A + A') / 2 instead of A's upper triangle (above); the IMM kernels keep the triangle
+// SYMM: P+ = (A + A') / 2 instead of A's upper triangle (above); kf_fast's packed builds and the IMM kernels (fk_imm.hpp,
+// imm_lanes.hip and its streamed copy lanes_update) all run SYMM = true
 template <int NX, int NZ, bool FAST_RCP = false, bool UPD_CACHE = true, bool SYMM = false, class Model>
 FK_HD int kf_update_sym(double (&x)[NX], double (&U)[NX * (NX + 1) / 2], const double (&z)[NZ], const Model &M,
                         double (&K)[NX * NZ], double (&y)[NZ], double (&S)[NZ * NZ],

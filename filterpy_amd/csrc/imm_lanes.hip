@@ -91,10 +91,11 @@ __device__ __forceinline__ void lanes_predict(double (&x)[NX], double (&U)[NX * 
     }
 }
 
-// kf_update_sym<NX, NZ, true> (fk_math_sym.hpp) the same way: H's and R's rows read where they are used (no register copy of the
-// model), the Joseph-form rows parked in the lane's column of the exchange image as they are produced instead of collected in a
-// second packed matrix: what is live at the peak is U, P H', K and one row -- 150 doubles instead of 250.  Same operations, same
-// order.  Returns status bits; y, Lf, dinv like kf_update_sym (the caller's likelihood).
+// kf_update_sym<NX, NZ, true, true, true> (fk_math_sym.hpp: fast reciprocal, both triangles) the same way: H's and R's rows read
+// where they are used (no register copy of the model), the Joseph-form rows parked in the lane's column of the exchange image as
+// they are produced instead of collected in a second packed matrix: what is live at the peak is U, P H', K and one row -- 150
+// doubles instead of 250.  Written to be the same operations in the same order; built only with FK_IL_STREAM_UPDATE = 1, which no
+// test does.  Returns status bits; y, Lf, dinv like kf_update_sym (the caller's likelihood).
 template <int NX, int NZ, class Model>
 __device__ __forceinline__ int lanes_update(double (&x)[NX], double (&U)[NX * (NX + 1) / 2], const double (&z)[NZ], const Model &M,
                                             double *park, double (&y)[NZ], double (&Lf)[NZ * NZ], double (&dinv)[NZ])
@@ -162,10 +163,17 @@ __device__ __forceinline__ int lanes_update(double (&x)[NX], double (&U)[NX * (N
             M.rowH(r, h);
             D[r] -= dot<NX>(t1, h);
         }
+        // both triangles (SYMM, fk_math_sym.hpp): row i adds its half to what row j < i parked
+        FK_UNROLL for (int j = 0; j < i; ++j) {
+            double acc = t1[j];
+            FK_UNROLL for (int r = 0; r < NZ; ++r) acc = fma(D[r], K[j * NZ + r], acc);
+            park[sym_idx<NX>(j, i) * 64] = fma(0.5, acc, park[sym_idx<NX>(j, i) * 64]);
+        }
+        FK_STAGE();
         FK_UNROLL for (int j = i; j < NX; ++j) {
             double acc = t1[j];
             FK_UNROLL for (int r = 0; r < NZ; ++r) acc = fma(D[r], K[j * NZ + r], acc);
-            park[sym_idx<NX>(i, j) * 64] = acc;
+            park[sym_idx<NX>(i, j) * 64] = (j > i) ? 0.5 * acc : acc;
         }
         FK_STAGE();
     }
@@ -478,7 +486,10 @@ imm_lanes_kernel(const ImmArgs a, const int NM, const int aos)
                 ml_wave_fence();
             } else {
                 double K[NX * NZ], S[NZ * NZ];
-                st |= kf_update_sym<NX, NZ, true>(x, P, z, mod, K, y, S, Lf, dinv);
+                                // (both triangles: SYMM.  The extended kernels read H's and R's rows where they are used, UPD_CACHE = false -- same values
+                //  into the same operations, bit-identical --: with the register copy their (9,4) builds are 83 .. 85 KB of code, without it
+                //  73 KB and 1.0 instead of 1.2 .. 1.3 KB of scratch; the plain kernels keep the copy that was measured faster for them)
+                st |= kf_update_sym<NX, NZ, true, !EXT, true>(x, P, z, mod, K, y, S, Lf, dinv);
             }
             double q = 0.0;
             if constexpr (NZ == 1) {

@@ -11,8 +11,8 @@
 //
 //   predict  F P by rows (row l of P broadcast by its owner), then (F P) F' + Q on the lane's own rows: the reference's association
 //   update   P H' rows local; S's rows dealt out over the quad (rows of P H' broadcast), gathered, L D L' and y replicated;
-//            K rows local; T1 = P - K (P H')' in place (P symmetric: (H P)' = P H', the one-lane kernels' packed arithmetic makes the
-//            same use of it), D = K R - T1 H', P+ = T1 + D K' with K's rows broadcast -- the Joseph form of fk_math_sym.hpp row by row
+//            K rows local; H P column by column as a sum over the group (P is NOT assumed symmetric: kf_ml.hip), T1 = P - K (H P) in
+//            place, D = K R - T1 H', P+ = T1 + D K' with K's rows broadcast -- the Joseph form of kf_mlg.hip
 //   across the filters (mixing, the bank's estimate, the normalisation of mu): a wave-private LDS image [element][lane] like
 //   imm_lanes.hip, the lane reading the columns of the lanes with ITS sub index (the same rows of the other filters); the
 //   dim_x^2 elements of the estimate's P are dealt out over the 4 G lanes of the bank.
@@ -105,6 +105,22 @@ __device__ __forceinline__ double grp_bcast(double v)
         hi = __builtin_amdgcn_update_dpp(hi, hi, ctrl, 0xf, banks, false);
         return __hiloint2double(hi, lo);
     }
+}
+// The sum of a value over the LPF lanes of the filter's group, in every lane of it: two quad-permute steps, and for eight lanes the
+// other quad's sum over row_shr:4 / row_shl:4 with the bank masks of grp_bcast.
+__device__ __forceinline__ double grp_sum(double v)
+{
+    v += quad_rot<0xB1>(v);      // quad_perm:[1,0,3,2]
+    v += quad_rot<0x4E>(v);      // quad_perm:[2,3,0,1]
+    if constexpr (LPF == 8) {
+        const int lo = __double2loint(v), hi = __double2hiint(v);
+        int plo = __builtin_amdgcn_update_dpp(lo, lo, 0x114, 0xf, 0xA, false);
+        int phi = __builtin_amdgcn_update_dpp(hi, hi, 0x114, 0xf, 0xA, false);
+        plo = __builtin_amdgcn_update_dpp(plo, lo, 0x104, 0xf, 0x5, false);
+        phi = __builtin_amdgcn_update_dpp(phi, hi, 0x104, 0xf, 0x5, false);
+        v += __hiloint2double(phi, plo);
+    }
+    return v;
 }
 // (k: a compile-time constant after unrolling; owner = lane k / R of the group)
 #define FK_Q_OWN_(o, v) grp_bcast<((o) < LPF ? (o) : 0)>(v)
@@ -203,20 +219,15 @@ __device__ __forceinline__ int quad_update(double (&x)[NX], double (&P)[NX / LPF
 {
     constexpr int R = NX / LPF, ZR = NZ / LPF;
     int st = 0;
-    LM M = quad_fresh(M0);
-    FK_UNROLL for (int r = 0; r < NZ; ++r) {
-        double h[NX];
-        M.rowH(r, h);
-        y[r] = z[r] - dot<NX>(h, x);
-    }
     double PHT[R][NZ];
-    M = quad_fresh(M0);
+    LM M = quad_fresh(M0);
     {
         double hr[2][NX];
         M.rowH(0, hr[0]);
         FK_UNROLL for (int c = 0; c < NZ; ++c) {
             if (c + 1 < NZ) M.rowH(c + 1, hr[(c + 1) & 1]);
             const double (&h)[NX] = hr[c & 1];
+            y[c] = z[c] - dot<NX>(h, x);                       // (row c of H serves y[c] and column c of P H' in one pass)
             FK_UNROLL for (int r = 0; r < R; ++r) {
                 double acc = P[r][0] * h[0];
                 FK_UNROLL for (int k = 1; k < NX; ++k) acc = fma(P[r][k], h[k], acc);
@@ -276,20 +287,30 @@ __device__ __forceinline__ int quad_update(double (&x)[NX], double (&P)[NX / LPF
         }
         FK_UNROLL for (int k = 0; k < NX; ++k) x[k] = FK_Q_OWNER(k, R, xo[k % R]);
     }
-    // Joseph form.  T1 = (I - K H) P = P - K (P H')' in place
-    // (the rows of P H' are broadcast a second time: as the same values as in S's phase the compiler kept the 128 broadcast doubles
-    //  of that phase alive -- in scratch memory -- instead)
-    FK_UNROLL for (int r = 0; r < R; ++r)
-        FK_UNROLL for (int c = 0; c < NZ; ++c) asm volatile("" : "+v"(PHT[r][c]));
-    FK_UNROLL for (int j = 0; j < NX; ++j) {
-        double prow[NZ];
-        FK_UNROLL for (int c = 0; c < NZ; ++c) prow[c] = FK_Q_OWNER(j, R, PHT[j % R][c]);
-        FK_UNROLL for (int r = 0; r < R; ++r) {
-            double acc = P[r][j];
-            FK_UNROLL for (int c = 0; c < NZ; ++c) acc = fma(-K[r * NZ + c], prow[c], acc);
-            P[r][j] = acc;
+    // Joseph form.  T1 = (I - K H) P = P - K (H P), column by column in place, WITHOUT assuming P symmetric: P is held by rows and
+    // its two triangles round differently; with (P H')' in the place of H P that rounding asymmetry is amplified instead of
+    // contracted (kf_ml.hip; docs/KERNEL_NOTES.md has the figures).  Column j of H P needs column j of P only: the lane's rows
+    // contribute sum_r H[c][sub R + r] P[r][j], the group adds its parts.
+    {
+        M = quad_fresh(M0);
+        const double *ho = M.s + LM::OFF_H + sub * (unsigned)R;
+        double hown[NZ][R];
+        FK_UNROLL for (int c = 0; c < NZ; ++c)
+            FK_UNROLL for (int r = 0; r < R; ++r) hown[c][r] = ho[c * LM::PX + r];
+        FK_UNROLL for (int j = 0; j < NX; ++j) {
+            double hp[NZ];
+            FK_UNROLL for (int c = 0; c < NZ; ++c) {
+                double acc = hown[c][0] * P[0][j];
+                FK_UNROLL for (int r = 1; r < R; ++r) acc = fma(hown[c][r], P[r][j], acc);
+                hp[c] = grp_sum(acc);
+            }
+            FK_UNROLL for (int r = 0; r < R; ++r) {
+                double acc = P[r][j];
+                FK_UNROLL for (int c = 0; c < NZ; ++c) acc = fma(-K[r * NZ + c], hp[c], acc);
+                P[r][j] = acc;
+            }
+            if (j % 4 == 3) FK_STAGE();            // (a fence every fourth column: the smallest code of every spacing tried)
         }
-        if (j % 2 == 1) FK_STAGE();
     }
     FK_STAGE();
     // D = K R - T1 H'
@@ -580,10 +601,9 @@ imm_quad_kernel(const ImmArgs a, const int NM, const int aos)
         } else {
             // posterior estimate of step t-1 and mixing for step t from one publication
             if (mmae) {
-                cbar = mu;                                          // p_i *= likelihood_i (mmae.py:186-187): no mixing
-                if (t > 0 && want_post)
-                    quad_exchange<false, NX, G, CH, PH>(ctx, x, P, mu, cbar, true, a.x_out ? a.x_out + (t - 1) * N * n : nullptr,
-                                                        a.P_out ? a.P_out + (t - 1) * N * nn : nullptr, true);
+                // p_i *= likelihood_i (mmae.py:186-187): no mixing; the step's posterior estimate is formed at its END (below): one
+                // instantiation of the exchange serves every MMAE step and the last step of an IMM call
+                cbar = mu;
             } else {
                 quad_exchange<true, NX, G, CH, PH>(ctx, x, P, mu, cbar, t > 0 && want_post, a.x_out ? a.x_out + (t - 1) * N * n : nullptr,
                                                    a.P_out ? a.P_out + (t - 1) * N * nn : nullptr);
@@ -659,10 +679,22 @@ imm_quad_kernel(const ImmArgs a, const int NM, const int aos)
             if (a.mu_out) (a.mu_out + t * N * NM)[oM.at(bank, (int)j)] = mu;
             if (a.L_out) (a.L_out + t * N * NM)[oM.at(bank, (int)j)] = lj;
         }
+        if constexpr (EXT) {
+            // the posterior estimate of this step where no mixing of a next step publishes it: every MMAE step, any call's last step
+            // (the last step through a value the optimiser cannot relate to the trip count: it peeled the last trip otherwise, the
+            //  whole step twice in the code)
+            long last = a.T - 1;
+            asm volatile("" : "+s"(last));
+            if (want_post && (mmae || t == last))
+                quad_exchange<false, NX, G, CH, PH>(ctx, x, P, mu, cbar, true, a.x_out ? a.x_out + t * N * n : nullptr,
+                                                     a.P_out ? a.P_out + t * N * nn : nullptr, mmae);
+        }
     }
-    if (want_post && a.T > 0 && !(EXT && a.phase == FK_IMM_PREDICT))      // the last step's posterior estimate
-        quad_exchange<false, NX, G, CH, PH>(ctx, x, P, mu, cbar, true, a.x_out ? a.x_out + (a.T - 1) * N * n : nullptr,
-                                            a.P_out ? a.P_out + (a.T - 1) * N * nn : nullptr, mmae);
+    if constexpr (!EXT) {
+        if (want_post && a.T > 0)                                          // the last step's posterior estimate
+            quad_exchange<false, NX, G, CH, PH>(ctx, x, P, mu, cbar, true, a.x_out ? a.x_out + (a.T - 1) * N * n : nullptr,
+                                                 a.P_out ? a.P_out + (a.T - 1) * N * nn : nullptr);
+    }
     {
         const RecMap mx = rec_map(aos, N, NM * n), mP = rec_map(aos, N, NM * n * n), mm = rec_map(aos, N, NM);
         bool fin = all_finite<NX>(x) && (fabs(mu) <= 1.79769313486231570815e+308);

@@ -35,12 +35,13 @@ def state_estimate(xs, Ps, mu):
     return x, P
 
 
-def imm_batch(xs0, Ps0, mu0, Mtrans, zs, Fs, Qs, Hs, Rs, Bs=None, us=None):
+def imm_batch(xs0, Ps0, mu0, Mtrans, zs, Fs, Qs, Hs, Rs, Bs=None, us=None, return_state=False):
     """T x { imm.predict(); imm.update(z) } for one IMM with len(Fs) linear models.
 
     xs0 (nm, n), Ps0 (nm, n, n): the filters' states; mu0 (nm,) (normalised like IMM.py:129).
     Returns per step: combined posterior x (T,n), P (T,n,n), mode probabilities (T,nm),
-    combined prior x, P, and the per-model likelihoods (T,nm)."""
+    combined prior x, P, and the per-model likelihoods (T,nm); with return_state also the filters' final
+    states xs (nm,n) and Ps (nm,n,n)."""
     nm = len(Fs)
     xs = [np.array(x, dtype=float) for x in xs0]
     Ps = [np.array(P, dtype=float) for P in Ps0]
@@ -90,15 +91,18 @@ def imm_batch(xs0, Ps0, mu0, Mtrans, zs, Fs, Qs, Hs, Rs, Bs=None, us=None):
         cbar, omega = mixing(mu, Mtrans)
         out_x[t], out_P[t] = state_estimate(xs, Ps, mu)
         out_mu[t], out_L[t] = mu, L
+    if return_state:
+        return out_x, out_P, out_mu, out_xp, out_Pp, out_L, np.array(xs), np.array(Ps)
     return out_x, out_P, out_mu, out_xp, out_Pp, out_L
 
 
-def mmae_batch(xs0, Ps0, p0, zs, Fs, Qs, Hs, Rs, Bs=None, us=None):
+def mmae_batch(xs0, Ps0, p0, zs, Fs, Qs, Hs, Rs, Bs=None, us=None, return_state=False):
     """T x { bank.predict(); bank.update(z) } of filterpy.kalman.MMAEFilterBank (mmae.py:140-212).
 
     No mixing; p_i *= likelihood_i, normalised with Python's sum (mmae.py:185-189); x = sum p_i x_i;
     the covariance loop zips the components of x with the filters (mmae.py:205-207) and is restated
-    as written.  Returns per step x (T,n), P (T,n,n), p (T,nm), likelihoods (T,nm)."""
+    as written.  Returns per step x (T,n), P (T,n,n), p (T,nm), likelihoods (T,nm); with return_state also the
+    filters' final states xs (nm,n) and Ps (nm,n,n)."""
     nm = len(Fs)
     xs = [np.array(x, dtype=float) for x in xs0]
     Ps = [np.array(P, dtype=float) for P in Ps0]
@@ -131,4 +135,6 @@ def mmae_batch(xs0, Ps0, p0, zs, Fs, Qs, Hs, Rs, Bs=None, us=None):
             y = xj - xk
             P += pj * (np.outer(y, y) + Pj)
         out_x[t], out_P[t], out_p[t], out_L[t] = x, P, p, L
+    if return_state:
+        return out_x, out_P, out_p, out_L, np.array(xs), np.array(Ps)
     return out_x, out_P, out_p, out_L

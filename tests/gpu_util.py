@@ -57,6 +57,40 @@ def run_kf_batch(x0, P0, zs, F, Q, H, R, *, layout="soa", mode=FK_MODEL_SHARED, 
     return res
 
 
+def run_imm(xs0, Ps0, mu0, M, zs, Fs, Qs, Hs, Rs, layout, phase=0, priors=True, zmask=None, ll0=None, mmae=False, check_status=True):
+    """fk_imm_batch_ex_f64 through the C ABI.  xs0 (N,nm,n), Ps0 (N,nm,n,n), mu0 (N,nm), zs (T,N,m) -> dict of host arrays.
+    zmask (T,N) uint8: 0 = update(None); ll0 (N,nm): the filters' zero-residual log-densities in (the final ones come back as
+    res["ll0"]); mmae: an MMAEFilterBank (M is None, no mixing, no priors); check_status=False: the caller looks at res["status"] itself."""
+    N, nm, n = xs0.shape
+    T, _, m = zs.shape
+    dxs = E.to_records(xs0.reshape(N, nm * n), layout, 0)
+    dPs = E.to_records(Ps0.reshape(N, nm * n * n), layout, 0)
+    dmu = E.to_records(mu0, layout, 0)
+    dz = E.to_records(zs, layout, 1)
+    out = dict(x_out=E.alloc_records((T,), N, n, layout), P_out=E.alloc_records((T,), N, n * n, layout),
+               mu_out=E.alloc_records((T,), N, nm, layout), likelihood_out=E.alloc_records((T,), N, nm, layout))
+    if priors and not mmae:
+        out.update(x_prior_out=E.alloc_records((T,), N, n, layout), P_prior_out=E.alloc_records((T,), N, n * n, layout))
+    for o in out.values():
+        o.fill_(float("nan"))
+    st = torch.zeros(N, dtype=torch.int32, device=dxs.device)
+    dmask = None if zmask is None else torch.as_tensor(np.ascontiguousarray(zmask, dtype=np.uint8), device=dxs.device)
+    dll0 = None if ll0 is None else E.to_records(ll0, layout, 0)
+    E.imm_batch(n, m, nm, N, T, layout, E.dev(Fs), E.dev(Qs), E.dev(Hs), E.dev(Rs), None if mmae else E.dev(M), dz, dxs, dPs, dmu,
+                status=st, phase=phase, zmask=dmask, ll0=dll0, mmae=mmae, **out)
+    torch.cuda.synchronize()
+    assert not (check_status and st.any())
+    shapes = dict(x_out=(n,), P_out=(n, n), mu_out=(nm,), likelihood_out=(nm,), x_prior_out=(n,), P_prior_out=(n, n))
+    res = {k: E.from_records(v, layout, 1, shapes[k]) for k, v in out.items()}
+    if dll0 is not None:
+        res["ll0"] = E.from_records(dll0, layout, 0, (nm,))
+    res["xs"] = E.from_records(dxs, layout, 0, (nm, n))
+    res["Ps"] = E.from_records(dPs, layout, 0, (nm, n, n))
+    res["mu"] = E.from_records(dmu, layout, 0, (nm,))
+    res["status"] = st.cpu().numpy()
+    return res
+
+
 def run_rts(Xs, Ps, F, Q, *, layout="soa", mode=FK_MODEL_SHARED, convention=0):
     """Xs (T,N,n), Ps (T,N,n,n) -> xs, Ps_out, K, Pp host arrays."""
     T, N, n = Xs.shape

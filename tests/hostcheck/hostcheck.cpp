@@ -494,17 +494,22 @@ extern "C" int hc_imm_batch(int n, int m, int nm, long T, const double *F, const
 {
 #define GO(NXV, NZV, NMV) \
     return imm_batch<NXV, NZV, NMV>(n, m, T, F, Q, H, R, Mt, z, xs0, Ps0, mu0, x_out, P_out, mu_out, xp_out, Pp_out, L_out, mmae)
-    const int cls = (n <= 2 && m <= 1) ? 0 : (n <= 4 && m <= 2) ? 1 : 2;
+    // (9,4) x 2 / 4 / 8: the classes imm_lanes.hip serves (its per-filter arithmetic is fk_imm.hpp's, same operations, same order)
+    const int cls = (n > 6 || m > 3) ? 3 : (n <= 2 && m <= 1) ? 0 : (n <= 4 && m <= 2) ? 1 : 2;
+    if (n > 9 || m > 4) return -1;
     if (nm == 2) {
         if (cls == 0) GO(2, 1, 2);
         if (cls == 1) GO(4, 2, 2);
-        GO(6, 3, 2);
+        if (cls == 2) GO(6, 3, 2);
+        GO(9, 4, 2);
     }
-    if (nm == 3) {
+    if (nm == 3 && cls < 3) {
         if (cls == 0) GO(2, 1, 3);
         if (cls == 1) GO(4, 2, 3);
         GO(6, 3, 3);
     }
+    if (nm == 4 && cls == 3) GO(9, 4, 4);
+    if (nm == 8 && cls == 3) GO(9, 4, 8);
 #undef GO
     return -1;
 }

@@ -21,44 +21,11 @@ def stable_F(rs, n):
     return F / max(1.0, 1.05 * np.max(np.abs(np.linalg.eigvals(F))))
 
 
-def run_imm(xs0, Ps0, mu0, M, zs, Fs, Qs, Hs, Rs, layout, phase=0, priors=True, zmask=None, ll0=None):
-    """xs0 (N,nm,n), Ps0 (N,nm,n,n), mu0 (N,nm), zs (T,N,m) -> dict of host arrays.  zmask (T,N) uint8: 0 = update(None);
-    ll0 (N,nm): the filters' zero-residual log-densities in (the final ones come back as res["ll0"])."""
-    import torch
-    from filterpy_amd import _engine as E
-    N, nm, n = xs0.shape
-    T, _, m = zs.shape
-    dxs = E.to_records(xs0.reshape(N, nm * n), layout, 0)
-    dPs = E.to_records(Ps0.reshape(N, nm * n * n), layout, 0)
-    dmu = E.to_records(mu0, layout, 0)
-    dz = E.to_records(zs, layout, 1)
-    out = dict(x_out=E.alloc_records((T,), N, n, layout), P_out=E.alloc_records((T,), N, n * n, layout),
-               mu_out=E.alloc_records((T,), N, nm, layout), likelihood_out=E.alloc_records((T,), N, nm, layout))
-    if priors:
-        out.update(x_prior_out=E.alloc_records((T,), N, n, layout), P_prior_out=E.alloc_records((T,), N, n * n, layout))
-    for o in out.values():
-        o.fill_(float("nan"))
-    st = torch.zeros(N, dtype=torch.int32, device=dxs.device)
-    dmask = None if zmask is None else torch.as_tensor(np.ascontiguousarray(zmask, dtype=np.uint8), device=dxs.device)
-    dll0 = None if ll0 is None else E.to_records(ll0, layout, 0)
-    E.imm_batch(n, m, nm, N, T, layout, E.dev(Fs), E.dev(Qs), E.dev(Hs), E.dev(Rs), E.dev(M), dz, dxs, dPs, dmu,
-                status=st, phase=phase, zmask=dmask, ll0=dll0, **out)
-    torch.cuda.synchronize()
-    assert not st.any()
-    shapes = dict(x_out=(n,), P_out=(n, n), mu_out=(nm,), likelihood_out=(nm,), x_prior_out=(n,), P_prior_out=(n, n))
-    res = {k: E.from_records(v, layout, 1, shapes[k]) for k, v in out.items()}
-    if dll0 is not None:
-        res["ll0"] = E.from_records(dll0, layout, 0, (nm,))
-    res["xs"] = E.from_records(dxs, layout, 0, (nm, n))
-    res["Ps"] = E.from_records(dPs, layout, 0, (nm, n, n))
-    res["mu"] = E.from_records(dmu, layout, 0, (nm,))
-    return res
-
-
 @pytest.mark.parametrize("layout", ["soa", "aos"])
 @pytest.mark.parametrize("n,m,nm", CASES)
 def test_imm_goldens(n, m, nm, layout):
     """every track of the bank runs the golden sequence (N not a multiple of the workgroup)."""
+    from gpu_util import run_imm
     from gpu_util import tile_tracks
     g = golden("imm")
     p = f"n{n}m{m}k{nm}_"
@@ -80,6 +47,7 @@ def test_imm_goldens(n, m, nm, layout):
 @pytest.mark.parametrize("n,m,nm", [(4, 2, 2), (4, 2, 3), (6, 3, 3)])
 def test_imm_seeded_bank_vs_oracle(n, m, nm, layout):
     """independent tracks (own states, measurements and mode probabilities) against the oracle."""
+    from gpu_util import run_imm
     from oracle import imm_oracle
     rs = np.random.RandomState(77 + n + nm)
     N, T = 1000, 25
@@ -113,6 +81,7 @@ def test_imm_extreme_likelihoods_vs_oracle(n, m, nm, layout):
     DBL_MIN, kalman_filter.py:1213-1226 -- the normalising sum is SUBNORMAL and its reciprocal would overflow), measurement
     noise of 1e-150 and 1e+150 (|S| beyond what a plain product of pivots can hold), next to ordinary tracks.  The kernel forms
     the density from the reciprocal pivots without a logarithm and normalises by a reciprocal (fk_imm.hpp)."""
+    from gpu_util import run_imm
     from oracle import imm_oracle
     rs = np.random.RandomState(5 + n + nm)
     N, T = 260, 6
@@ -152,6 +121,7 @@ def test_imm_chunked_call_is_bit_identical(n, m, nm, N, layout, monkeypatch):
     """FK_IMM_CHUNKS="G,H" cuts fk_imm_batch_f64 into bank groups x time chunks on helper streams (fk_chunks.hpp, imm_chunked_call),
     the state handed from chunk to chunk through xs / Ps / mu in place: every output, the final state and the status must be
     bit-identical to the single launch -- the register-resident and the rolled classes, ragged last workgroups."""
+    from gpu_util import run_imm
     rs = np.random.RandomState(3 * n + nm + N % 7)
     T = 23
     Fs = np.array([stable_F(rs, n) for _ in range(nm)])
@@ -186,6 +156,7 @@ def test_imm_chunked_call_with_missing_measurements_is_bit_identical(n, m, nm, N
     step -- in registers inside one launch, through ll0 between the pieces of a chunked call.  A masked call WITHOUT ll0 cannot
     hand it over and must therefore stay one launch; with ll0 every decomposition is bit-identical.  Missing measurements sit
     right behind every chunk boundary of the decompositions tried."""
+    from gpu_util import run_imm
     rs = np.random.RandomState(5 * n + nm)
     T = 24
     Fs = np.array([stable_F(rs, n) for _ in range(nm)])
@@ -302,6 +273,7 @@ def _big_file(nm):
 @pytest.mark.parametrize("n,m,nm", _big("imm") + _big("imm", "imm_banks16"))
 def test_big_imm_banks_vs_live_reference(n, m, nm, layout):
     """IMMEstimator on banks the round-2 kernel refused: every track of a ragged bank runs the live reference's sequence"""
+    from gpu_util import run_imm
     from gpu_util import tile_tracks
     g = golden(_big_file(nm))
     p = f"imm_n{n}m{m}k{nm}_"
@@ -321,6 +293,7 @@ def test_big_imm_banks_vs_live_reference(n, m, nm, layout):
 @pytest.mark.parametrize("n,m,nm", [(9, 3, 4), (5, 4, 8), (3, 1, 6)])
 def test_big_imm_seeded_bank_vs_oracle(n, m, nm, layout):
     """independent tracks (own states, measurements, mode probabilities) on the big banks, against the oracle"""
+    from gpu_util import run_imm
     from oracle import imm_oracle
     rs = np.random.RandomState(177 + n + nm)
     N, T = 200, 10
@@ -587,6 +560,7 @@ def test_imm_banks_above_9_4_vs_oracle(n, m, nm, layout):
     """VERDICT r3 missing 3: IMMEstimator takes filters of any size (IMM.py:14-120); the kernels stopped at dim_x 9 / dim_z 4.
     The classes (12, 4) / (16, 8) (csrc/imm_quad.hip; rounds 4-6: a rolled one-lane-per-bank class) against the oracle: independent tracks, a ragged last workgroup, all outputs,
     and the class API on the same bank."""
+    from gpu_util import run_imm
     from filterpy_amd.kalman import IMMEstimator, KalmanFilter
     from oracle import imm_oracle
     rs = np.random.RandomState(7 + n + 3 * nm)
@@ -651,6 +625,7 @@ def _lanes_bank(n, m, nm, N, T, seed):
 def test_imm_lanes_kernel_vs_oracle(n, m, nm, layout):
     """banks the one-lane-per-filter kernel (and, above (9,4), the four-lanes-per-filter kernel) serves (IMM.py:160-249), N not a multiple of the banks of a wave or a block, every
     bank checked at its ends: per-step estimate, prior, mode probabilities, likelihoods and the bank's final state"""
+    from gpu_util import run_imm
     from oracle import imm_oracle
     N, T = 203, 7
     b = _lanes_bank(n, m, nm, N, T, 500 + 10 * n + nm)
@@ -677,6 +652,7 @@ def test_imm_lanes_kernel_vs_oracle(n, m, nm, layout):
 def test_imm_lanes_kernel_output_subsets(outs, layout, dims):
     """any subset of the per-step outputs (the pointers are tested at run time): what is asked for equals the all-outputs call
     bit for bit, and so does the final state of the bank"""
+    from gpu_util import run_imm
     import torch
     from filterpy_amd import _engine as E
     (n, m, nm), N, T = dims, 77, 5
@@ -715,11 +691,12 @@ def test_imm_lanes_kernel_against_the_one_lane_per_bank_kernels():
 import sys, numpy as np
 sys.path.insert(0, "tests")
 import test_gpu_imm as t
+from gpu_util import run_imm
 res = {}
 for (n, m, nm) in [(6, 3, 3), (4, 2, 2), (2, 1, 3), (5, 2, 2)]:
     b = t._lanes_bank(n, m, nm, 150, 6, 9 + nm)
     for layout in ("soa", "aos"):
-        r = t.run_imm(*b, layout)
+        r = run_imm(*b, layout)
         for k in ("x_out", "P_out", "mu_out", "likelihood_out", "x_prior_out", "P_prior_out", "xs", "Ps", "mu"):
             res[f"{n}_{m}_{nm}_{layout}_{k}"] = r[k]
 np.savez(sys.argv[1], **res)
@@ -751,11 +728,12 @@ def test_imm_eight_lanes_per_filter_against_four():
 import sys, numpy as np
 sys.path.insert(0, "tests")
 import test_gpu_imm as t
+from gpu_util import run_imm
 res = {}
 for (n, m, nm) in [(16, 8, 2), (13, 5, 2), (10, 7, 2)]:
     b = t._lanes_bank(n, m, nm, 150, 6, 19 + n)
     for layout in ("soa", "aos"):
-        r = t.run_imm(*b, layout)
+        r = run_imm(*b, layout)
         for k in ("x_out", "P_out", "mu_out", "likelihood_out", "x_prior_out", "P_prior_out", "xs", "Ps", "mu"):
             res[f"{n}_{m}_{nm}_{layout}_{k}"] = r[k]
 np.savez(sys.argv[1], **res)

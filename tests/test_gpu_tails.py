@@ -26,7 +26,7 @@ def stable_F(rs, n):
 @pytest.mark.parametrize("n,m,nm", [(2, 1, 2), (4, 2, 3), (6, 3, 2), (3, 2, 2)])
 def test_imm_tails(n, m, nm, layout):
     from oracle import imm_oracle
-    from test_gpu_imm import run_imm
+    from gpu_util import run_imm
     rs = np.random.RandomState(n * 100 + nm)
     Fs = np.array([stable_F(rs, n) for _ in range(nm)])
     Qs = np.array([spd(rs, n, 0.05 * (j + 1)) for j in range(nm)])
