@@ -676,3 +676,132 @@ extern "C" void hc_det_from_dinv(int m, const double *dinv, double *logdet, doub
     *logdet = fk::logdet_from_dinv<4>(d, m);
     *rsqrt_det = fk::rsqrt_det_from_dinv<4>(d, m);
 }
+
+
+// ---------------------------------------------------------------------------------------------------------
+// Chunked calls (filterpy_amd/csrc/fk_chunk_plan.hpp: the policy, the pieces and the driver that libfilterhip runs on HIP
+// streams) on recording lanes: every fork, wait, piece and join in order, the pieces' pointers as element offsets.
+#include <cstddef>
+
+#include "../../filterpy_amd/csrc/fk_chunk_plan.hpp"
+
+namespace chunks {
+
+// a pointer of the fake argument blocks: member number k of a block starts at k * 1e9, NULL is -1
+struct Ptr {
+    long at = -1;
+    Ptr(std::nullptr_t = nullptr) {}
+    explicit Ptr(long a) : at(a) {}
+    explicit operator bool() const { return at >= 0; }
+    Ptr operator+(long d) const { return Ptr(at + d); }
+};
+
+// the members that the pieces of KfArgs, RtsArgs, ImmArgs, UkfRtsArgs and UkfArgs (fk_kernel_args.hpp) differ in
+struct Kf {
+    Ptr F, Q, H, R, B, u, z, mask, means, covs, means_p, covs_p, y_out, K_out, S_out, SI_out, ll_out, maha_out;
+    int extras_per_step, nu, model_t, status_or;
+    long N, T, i0, cnt, cov_step;
+    template <class V> void each(V &&v) { v(F), v(Q), v(H), v(R), v(B), v(u), v(z), v(mask), v(means), v(covs), v(means_p), v(covs_p), v(y_out), v(K_out), v(S_out), v(SI_out), v(ll_out), v(maha_out); }
+};
+struct Rts {
+    Ptr Xs, Ps, xs, Ps_out, K, Pp;
+    int cont, status_or;
+    long N, T, i0, cnt;
+    template <class V> void each(V &&v) { v(Xs), v(Ps), v(xs), v(Ps_out), v(K), v(Pp); }
+};
+struct Imm {
+    Ptr z, mask, u, ll0, x_out, P_out, mu_out, xp_out, Pp_out, L_out;
+    int nu, status_or;
+    long N, T, i0, cnt;
+    template <class V> void each(V &&v) { v(z), v(mask), v(u), v(ll0), v(x_out), v(P_out), v(mu_out), v(xp_out), v(Pp_out), v(L_out); }
+};
+struct UkfRts {
+    Ptr Xs, Ps, xs, ps, Ks;
+    int cont, status_or;
+    long N, T, i0, cnt;
+    template <class V> void each(V &&v) { v(Xs), v(Ps), v(xs), v(ps), v(Ks); }
+};
+struct Ukf {
+    Ptr z, mask, means, covs;
+    int status_or;
+    long N, T, i0, cnt;
+    template <class V> void each(V &&v) { v(z), v(mask), v(means), v(covs); }
+};
+inline int cont_of(const Rts &a) { return a.cont; }
+inline int cont_of(const UkfRts &a) { return a.cont; }
+template <class A> int cont_of(const A &) { return 0; }
+
+enum { FORK = 0, WAIT = 1, PIECE = 2, JOIN = 3 };
+
+// the trace: rows of longs -- FORK | WAIT g | JOIN g | PIECE g i0 cnt T status_or cont <the block's pointers>
+struct Trace {
+    long *out, cap, n = 0;
+    void put(long v) { if (n < cap) out[n] = v; ++n; }
+};
+
+struct Lanes {
+    Trace &tr;
+    int stream(int g) const { return g; }
+    bool fork() { tr.put(FORK); return true; }
+    bool wait(int g) { tr.put(WAIT), tr.put(g); return true; }
+    bool join(int g) { tr.put(JOIN), tr.put(g); return true; }
+};
+
+// every member of the block set: pointers to their bases -- those named in `null` (a bit per member) stay NULL
+template <class A>
+A block(const long *cfg, unsigned null)
+{
+    A a = {};
+    int k = 0;
+    a.each([&](Ptr &p) { p = (null >> k & 1) ? Ptr() : Ptr(k * 1000000000L); ++k; });
+    a.N = cfg[0], a.T = cfg[1], a.i0 = cfg[2], a.cnt = cfg[3], a.status_or = (int)cfg[4];
+    return a;
+}
+
+// launches fail from piece number fail_at on (-1: never) with the code 7
+template <class A>
+auto recorder(Trace &tr, long fail_at, long &pieces)
+{
+    return [&tr, fail_at, &pieces](const A &b, int g) -> int {
+        A c = b;
+        tr.put(PIECE), tr.put(g), tr.put(b.i0), tr.put(b.cnt), tr.put(b.T), tr.put(b.status_or), tr.put(cont_of(b));
+        c.each([&](Ptr &p) { tr.put(p.at); });
+        return pieces++ == fail_at ? 7 : 0;
+    };
+}
+
+}  // namespace chunks
+
+// cfg: N, T, i0, cnt, status_or, slots, n, m, then per family (0 forward filter, 1 smoother, 2 IMM, 3 UKF smoother, 4 fused
+// UKF) what its call takes: 0: tracks_per_wave, group_quantum, model_t, nu, extras_per_step, cov_step; 2: nm, nu; 3: cont.
+// null: the members that stay NULL.  Returns how many longs the trace has (out[0]: what the call returned), -1: unknown family.
+extern "C" long hc_chunk_trace(int family, const long *cfg, unsigned null, long fail_at, long *out, long cap)
+{
+    using namespace chunks;
+    Trace tr{out, cap};
+    Lanes lanes{tr};
+    long pieces = 0;
+    const long slots = cfg[5];
+    const int n = (int)cfg[6], m = (int)cfg[7];
+    int rc = -1;
+    tr.put(0);
+    if (family == 0) {
+        Kf a = block<Kf>(cfg, null);
+        a.model_t = (int)cfg[10], a.nu = (int)cfg[11], a.extras_per_step = (int)cfg[12], a.cov_step = cfg[13];
+        rc = fk::kf_chunked(a, n, m, slots, (int)cfg[8], cfg[9], lanes, recorder<Kf>(tr, fail_at, pieces));
+    } else if (family == 1) {
+        rc = fk::rts_chunked(block<Rts>(cfg, null), n, slots, lanes, recorder<Rts>(tr, fail_at, pieces));
+    } else if (family == 2) {
+        Imm a = block<Imm>(cfg, null);
+        a.nu = (int)cfg[9];
+        rc = fk::imm_chunked(a, n, m, (int)cfg[8], slots, lanes, recorder<Imm>(tr, fail_at, pieces));
+    } else if (family == 3) {
+        UkfRts a = block<UkfRts>(cfg, null);
+        a.cont = (int)cfg[8];
+        rc = fk::ukf_rts_chunked(a, n, slots, lanes, recorder<UkfRts>(tr, fail_at, pieces));
+    } else if (family == 4) {
+        rc = fk::ukf_chunked(block<Ukf>(cfg, null), n, m, lanes, recorder<Ukf>(tr, fail_at, pieces));
+    } else return -1;
+    if (cap > 0) out[0] = rc;
+    return tr.n;
+}
