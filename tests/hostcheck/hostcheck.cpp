@@ -211,6 +211,7 @@ extern "C" int hc_rts_sym(int n, long T, const double *F, const double *Q, const
     if (n == 2) return rts_sym<2>(T, F, Q, Xs, Ps, xs, Pso, Ko, Ppo);
     if (n == 4) return rts_sym<4>(T, F, Q, Xs, Ps, xs, Pso, Ko, Ppo);
     if (n == 6) return rts_sym<6>(T, F, Q, Xs, Ps, xs, Pso, Ko, Ppo);
+    if (n == 8) return rts_sym<8>(T, F, Q, Xs, Ps, xs, Pso, Ko, Ppo);
     if (n == 9) return rts_sym<9>(T, F, Q, Xs, Ps, xs, Pso, Ko, Ppo);
     return -1;
 }

@@ -48,6 +48,15 @@ def hc_rts(Xs, Ps, F, Q):
     return xs, Pso, K, Pp, st
 
 
+def hc_rts_sym(Xs, Ps, F, Q):
+    """rts_step_sym (dim_x 1, 2, 4, 6, 8, 9): the upper triangle of every covariance is what it reads"""
+    T, n = Xs.shape
+    c = np.ascontiguousarray
+    xs, Pso, K, Pp = np.zeros((T, n)), np.zeros((T, n, n)), np.zeros((T, n, n)), np.zeros((T, n, n))
+    st = lib().hc_rts_sym(n, ctypes.c_long(T), _p(c(F)), _p(c(Q)), _p(c(Xs)), _p(c(Ps)), _p(xs), _p(Pso), _p(K), _p(Pp))
+    return xs, Pso, K, Pp, st
+
+
 DIMS = [tuple(d) for d in golden("kf_dims")["dims"]]
 
 
@@ -143,12 +152,7 @@ def test_rts_packed_symmetric_vs_golden(n, m):
     """rts_step_sym (packed symmetric, row-streamed) -- the arithmetic of the exact-dim RTS kernels."""
     g = golden("kf_dims")
     p = f"n{n}m{m}_"
-    Xs, Ps = g[p + "plain_mu"], g[p + "plain_cov"]
-    T = Xs.shape[0]
-    c = np.ascontiguousarray
-    xs, Pso, K, Pp = np.zeros((T, n)), np.zeros((T, n, n)), np.zeros((T, n, n)), np.zeros((T, n, n))
-    st = lib().hc_rts_sym(n, ctypes.c_long(T), _p(c(g[p + "F"])), _p(c(g[p + "Q"])), _p(c(Xs)), _p(c(Ps)),
-                          _p(xs), _p(Pso), _p(K), _p(Pp))
+    xs, Pso, K, Pp, st = hc_rts_sym(g[p + "plain_mu"], g[p + "plain_cov"], g[p + "F"], g[p + "Q"])
     assert st == 0
     for got, key in ((xs, "rts_x"), (Pso, "rts_P"), (K, "rts_K"), (Pp, "rts_Pp")):
         assert rel_err_rows(got, g[p + key]) < 1e-9, key
