@@ -35,6 +35,7 @@
 #include "fk_kernel_args.hpp"
 #include "fk_ml.hpp"
 #include "fk_chunks.hpp"
+#include "fk_tickets.hpp"
 #include "../../include/filterhip.h"
 
 #ifndef FK_ML_WAVES
@@ -109,6 +110,15 @@ __device__ __forceinline__ void store_x(const MlView &v, const double (&x)[NX])
     }
 }
 
+// Track trk's x and this lane's R rows of P in the hand-over block of a ticket grid (fk_tickets.hpp): [NX + NX * NX][N], element-major
+// whatever the call's layout (NumPy-order x / P in place: 8-byte accesses to 64 lines per instruction); load<16> / store<16> (sc1).
+template <int R, int NX>
+struct MlHandover {
+    const MlView x, P;
+    __device__ __forceinline__ MlHandover(const double *ws, long N, long trk, unsigned Lc)
+        : x(ws, (unsigned)trk * 8u, (unsigned)N * 8u), P(ws + (long)NX * N, (unsigned)trk * 8u + Lc * (unsigned)(R * NX) * ((unsigned)N * 8u), (unsigned)N * 8u) {}
+};
+
 // AOS ([track][element], NumPy order) output of one (x, P) set: a wave's 16 tracks are one contiguous
 // slab of 16 * E doubles; the quads write their rows into a wave-private LDS tile laid out like the
 // slab, then the 64 lanes copy consecutive 16-byte units (1 KiB per store instruction).  The buffer
@@ -165,16 +175,9 @@ __device__ __forceinline__ void ml_store_soa_slab(const double (&x)[NX], const d
 // contiguous bytes per store instruction) at the two points of the step where a set is complete -- instead of the PAIRS
 // scheme's DPP half-exchange per pair (136 v_mov_dpp + the store-data hazard nops per step, in a kernel bound by VALU
 // issue).  Any N (an odd tail's last track leaves as 8 bytes).  FK_ML_SLAB=0 selects the PAIRS / 8-byte instantiations.
-// PERS (round 4): a persistent grid instead of one workgroup per 64 tracks for all T steps.  Every wave runs the same T steps, so
-// W waves on S wave slots cost ceil(W / S) rounds: configs[2]'s 6250 waves on 2048 slots pay for a fourth round that is 5 %
-// full (measured: 2 / 3 / 4 whole rounds 2.18 / 3.04 / 4.03 ms, N = 1e5 3.40 ms).  The multi-stream tail filling of
-// fk_chunks.hpp returns 1-4 % of that -- every piece is a kernel with its own launch gap and its own tail.  Here the call is
-// cut into G = ceil(N / 64) track groups x H time chunks and 512 resident workgroups draw TICKETS, chunk-major (all groups'
-// chunk h before any chunk h + 1): a workgroup that finishes early simply takes the next ticket.  Chunk h of a group needs
-// chunk h - 1 of the same group: its ticket is at least G >= 512 draws older, i.e. held by a workgroup that is running or
-// done -- no deadlock whatever is resident; the state travels through an element-major hand-over block of the call's scratch
-// allocation, written and read with agent-scope (sc1) accesses -- coherent across the XCDs' L2s without write-backs; NumPy-order
-// x / P in place would make them 8-byte accesses to 64 different lines per instruction -- and announced by a completion word.  Same arithmetic per track: results are bit-identical to the single launch.
+// PERS (round 4): a persistent ticket grid (fk_tickets.hpp: the plan, the scratch, the protocol) instead of one workgroup per 64 tracks for
+// all T steps.  Every wave runs the same T steps, so W waves on S slots cost ceil(W / S) rounds: configs[2]'s 6250 waves on 2048 slots pay for a
+// fourth round that is 5 % full (2 / 3 / 4 whole rounds 2.18 / 3.04 / 4.03 ms, N = 1e5 3.40); the multi-stream tail filling returns 1-4 % of it.
 template <int R, int NZ, bool OUTS, int WAVES, bool PAIRS, bool MASK, int LAYOUT, bool VAR = false, bool UF = false, bool SLAB = false, bool PERS = false>
 __global__ void __launch_bounds__(BLOCK, WAVES)
 kf_ml_kernel(const KfArgs a_in)
@@ -232,18 +235,14 @@ kf_ml_kernel(const KfArgs a_in)
     for (;;) {                                                   // PERS: one trip per ticket; otherwise exactly one trip
     unsigned bid = blockIdx.x;
     if constexpr (PERS) {
-        __syncthreads();                                         // the previous ticket's LDS traffic is over, s_task is free
-        if (threadIdx.x == 0) s_task = atomicAdd(a_in.pers_ctl, 1);
-        __syncthreads();
-        const int task = __builtin_amdgcn_readfirstlane(s_task);
-        const int G = a_in.pers_G, H = a_in.pers_H;
-        if (task >= G * H) break;
-        pers_h = task / G;
-        pers_g = task - pers_h * G;
+        const int task = ticket_draw(a_in.pers_ctl, s_task);
+        if (task >= a_in.pers_G * a_in.pers_H) break;
+        const TicketWindow w = ticket_window(task, a_in.pers_G, a_in.pers_H, a_in.T, false);
+        pers_h = w.chunk, pers_g = w.g;
         bid = (unsigned)pers_g;
-        const long t0 = a_in.T * pers_h / H, t1 = a_in.T * (pers_h + 1) / H, NN = a_in.N;
+        const long t0 = w.t0, NN = a_in.N;
         a = a_in;
-        a.T = t1 - t0;
+        a.T = w.t1 - t0;
         a.z = a_in.z + t0 * NN * NZ;
         a.mask = a_in.mask ? a_in.mask + t0 * NN : nullptr;
         a.means = a_in.means + t0 * NN * (3 * R);
@@ -251,13 +250,7 @@ kf_ml_kernel(const KfArgs a_in)
         a.covs = a_in.covs + t0 * NN * (9 * R * R);
         a.covs_p = a_in.covs_p + t0 * NN * (9 * R * R);
         a.status_or = t0 > 0 ? 1 : a_in.status_or;
-        if (pers_h > 0) {
-            // (the state is then read with agent-scope loads: no acquire fence, i.e. no L2 invalidation, is needed)
-            if (threadIdx.x == 0) {
-                while (__hip_atomic_load(&a_in.pers_ctl[1 + pers_g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < pers_h) __builtin_amdgcn_s_sleep(8);
-            }
-            __syncthreads();
-        }
+        ticket_wait(a_in.pers_ctl, pers_g, pers_h);
     }
 
     const long N = a.N;
@@ -306,13 +299,11 @@ kf_ml_kernel(const KfArgs a_in)
     double P[R][NX], x[NX];
     {
         if (PERS && pers_h > 0) {
-            // a later chunk of the group: the state the previous chunk left in the hand-over block (element-major whatever the
-            // layout: 512 contiguous bytes per wave instruction; agent-scope loads)
-            const unsigned n8 = (unsigned)N * 8u;
-            const MlView wx(a_in.pers_ws, (unsigned)trk * 8u, n8), wP(a_in.pers_ws + (long)NX * N, (unsigned)trk * 8u + Lc * (unsigned)(R * NX) * n8, n8);
+            // a later chunk of the group: the state the previous chunk left in the hand-over block
+            const MlHandover<R, NX> ho(a_in.pers_ws, N, trk, Lc);
             FK_UNROLL for (int r = 0; r < R; ++r)
-                FK_UNROLL for (int c = 0; c < NX; ++c) P[r][c] = wP.template load<HAUX>(r * NX + c);
-            FK_UNROLL for (int k = 0; k < NX; ++k) x[k] = wx.template load<HAUX>(k);
+                FK_UNROLL for (int c = 0; c < NX; ++c) P[r][c] = ho.P.template load<HAUX>(r * NX + c);
+            FK_UNROLL for (int k = 0; k < NX; ++k) x[k] = ho.x.template load<HAUX>(k);
         } else {
             const MlView vP(a.P, off_rows, estride), vx(a.x, t8, estride);
             FK_UNROLL for (int r = 0; r < R; ++r)
@@ -626,11 +617,10 @@ kf_ml_kernel(const KfArgs a_in)
             FK_UNROLL for (int c = 0; c < NX; ++c) fin = fin && (fabs(P[r][c]) <= 1.79769313486231570815e+308);
         if (PERS && pers_h + 1 < a_in.pers_H) {
             // not the group's last chunk: the state goes to the hand-over block (agent-scope stores), x / P stay untouched
-            const unsigned n8 = (unsigned)N * 8u;
-            const MlView wx(a_in.pers_ws, (unsigned)trk * 8u, n8), wP(a_in.pers_ws + (long)NX * N, (unsigned)trk * 8u + Lc * (unsigned)(R * NX) * n8, n8);
-            FK_UNROLL for (int k = 0; k < NX; ++k) wx.template store<HAUX>(k, x[k]);
+            const MlHandover<R, NX> ho(a_in.pers_ws, N, trk, Lc);
+            FK_UNROLL for (int k = 0; k < NX; ++k) ho.x.template store<HAUX>(k, x[k]);
             FK_UNROLL for (int r = 0; r < R; ++r)
-                FK_UNROLL for (int c = 0; c < NX; ++c) wP.template store<HAUX>(r * NX + c, P[r][c]);
+                FK_UNROLL for (int c = 0; c < NX; ++c) ho.P.template store<HAUX>(r * NX + c, P[r][c]);
         } else {
             const MlView vx(a.x, t8, estride), vP(a.P, off_rows, estride);
             FK_UNROLL for (int k = 0; k < NX; ++k) vx.store(k, x[k]);
@@ -640,29 +630,14 @@ kf_ml_kernel(const KfArgs a_in)
         if (a.status) {
             int s = st | (fin ? 0 : ST_NONFINITE);
             s |= __builtin_amdgcn_mov_dpp(s, 0x55 * 1, 0xf, 0xf, true) | __builtin_amdgcn_mov_dpp(s, 0x55 * 2, 0xf, 0xf, true);
-            if constexpr (PERS) {
-                if (L == 0) {
-                    const int old = a.status_or ? __hip_atomic_load(&a.status[trk], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-                    __hip_atomic_store(&a.status[trk], old | s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            } else {
-                if (L == 0) a.status[trk] = a.status_or ? (a.status[trk] | s) : s;
+            if (L == 0) {
+                if constexpr (PERS) status_merge_agent(a.status, trk, a.status_or, s);
+                else a.status[trk] = a.status_or ? (a.status[trk] | s) : s;
             }
         }
     }
-    if constexpr (PERS) {
-        // this chunk's final state (and status) is in place -- written with agent-scope stores, which are coherent across the
-        // XCDs by themselves (a release FENCE here writes back the whole L2 the kernel is streaming 14 GB of outputs through:
-        // measured 0.55 ms per chunk).  They are COMPLETE only once this wave's vmcnt has drained: a workgroup barrier does not
-        // wait for VMEM on gfx950 (the compiler emits `s_waitcnt vmcnt(63)` -- nothing -- in front of s_barrier; ADVICE r4: with
-        // status == NULL no other wait stood between the hand-over stores and the flag), so every wave drains explicitly --
-        // inline asm, invisible to the pass that drops "redundant" waits -- then the barrier, then the chunk is published
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_store(&a_in.pers_ctl[1 + pers_g], pers_h + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-        break;
-    }
+    if constexpr (!PERS) break;
+    else ticket_publish(a_in.pers_ctl, pers_g, pers_h + 1);      // this chunk's final state (and status) is in place
     }      // tickets
 }
 
@@ -706,12 +681,8 @@ __device__ __forceinline__ void ml_store_rows_aos_park(const double (&M)[R][NX],
 // every lane on a gathered packed copy (45 doubles) and each lane back-substitutes its own three
 // rows of K.  The filtered P is read twice (second time from L2) instead of being held across the
 // factorisation.  Shared constant F, Q; SOA; K and Pp outputs both present.
-// PERS (round 6): the forward kernel's persistent grid (see kf_ml_kernel) for the smoother -- G track groups x H time chunks drawn
-// as tickets by 2 workgroups per CU, chunk-major from the END of the time axis (a chunk needs the smoothed state of the first step
-// of the chunk after it in time: the ticket of that one is at least G draws older).  The state travels through the element-major
-// hand-over block with agent-scope accesses and is announced by the group's completion word; the window of a later-drawn chunk
-// overlaps its predecessor's by the one step it starts from (the `cont` convention of the chunked calls), whose outputs it leaves
-// alone.  Same arithmetic per track: bit-identical to the single launch.
+// PERS (round 6): the forward kernel's ticket grid for the smoother, chunk-major from the END of the time axis; the window of a
+// later-drawn chunk overlaps its predecessor's by the step it starts from (`cont`), whose outputs it leaves alone.  Bit-identical.
 template <int R, int WAVES, int MODE, bool PERS = false>
 __global__ void __launch_bounds__(BLOCK, WAVES)
 rts_ml_kernel(const RtsArgs a_in)
@@ -734,20 +705,15 @@ rts_ml_kernel(const RtsArgs a_in)
     for (;;) {                                                   // PERS: one trip per ticket; otherwise exactly one trip
     unsigned bid = blockIdx.x;
     if constexpr (PERS) {
-        __syncthreads();                                         // the previous ticket's LDS traffic is over, s_task is free
-        if (threadIdx.x == 0) s_task = atomicAdd(a_in.pers_ctl, 1);
-        __syncthreads();
-        const int task = __builtin_amdgcn_readfirstlane(s_task);
-        const int G = a_in.pers_G, H = a_in.pers_H;
-        if (task >= G * H) break;
-        pers_c = task / G;                                       // chunk number counted from the END of the time axis
-        pers_g = task - pers_c * G;
+        const int task = ticket_draw(a_in.pers_ctl, s_task);
+        if (task >= a_in.pers_G * a_in.pers_H) break;
+        const TicketWindow w = ticket_window(task, a_in.pers_G, a_in.pers_H, a_in.T, true);
+        pers_c = w.chunk, pers_g = w.g;                          // chunk number counted from the END of the time axis
         bid = (unsigned)pers_g;
-        const long hh = H - 1 - pers_c;
-        const long t0 = a_in.T * hh / H, t1 = a_in.T * (hh + 1) / H, NN = a_in.N;
+        const long t0 = w.t0, NN = a_in.N;
         a = a_in;
-        a.cont = pers_c > 0 ? 1 : 0;
-        a.T = t1 - t0 + (pers_c > 0 ? 1 : 0);                    // (+ the step the chunk starts from, smoothed by the chunk before it)
+        a.cont = w.cont ? 1 : 0;
+        a.T = w.t1 - t0 + (w.cont ? 1 : 0);                      // (+ the step the chunk starts from, smoothed by the chunk before it)
         a.Xs = a_in.Xs + t0 * NN * NX;
         a.xs = a_in.xs + t0 * NN * NX;
         a.Ps = a_in.Ps + t0 * NN * (NX * NX);
@@ -755,12 +721,7 @@ rts_ml_kernel(const RtsArgs a_in)
         a.K = a_in.K + t0 * NN * (NX * NX);
         a.Pp = a_in.Pp + t0 * NN * (NX * NX);
         a.status_or = pers_c > 0 ? 1 : a_in.status_or;
-        if (pers_c > 0) {
-            if (threadIdx.x == 0) {
-                while (__hip_atomic_load(&a_in.pers_ctl[1 + pers_g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < pers_c) __builtin_amdgcn_s_sleep(8);
-            }
-            __syncthreads();
-        }
+        ticket_wait(a_in.pers_ctl, pers_g, pers_c);
     }
     const long N = a.N, T = a.T;
     const unsigned L = threadIdx.x & 3u;
@@ -788,11 +749,10 @@ rts_ml_kernel(const RtsArgs a_in)
     double xn[NX], Pn[R][NX];
     if (PERS && a.cont) {
         // a later ticket of the group: the smoothed state of step T-1 of this window, from the hand-over block
-        const unsigned n8 = (unsigned)N * 8u;
-        const MlView wx(a_in.pers_ws, (unsigned)trk * 8u, n8), wP(a_in.pers_ws + (long)NX * N, (unsigned)trk * 8u + Lc * (unsigned)(R * NX) * n8, n8);
-        FK_UNROLL for (int k = 0; k < NX; ++k) xn[k] = wx.template load<HAUX>(k);
+        const MlHandover<R, NX> ho(a_in.pers_ws, N, trk, Lc);
+        FK_UNROLL for (int k = 0; k < NX; ++k) xn[k] = ho.x.template load<HAUX>(k);
         FK_UNROLL for (int r = 0; r < R; ++r)
-            FK_UNROLL for (int c = 0; c < NX; ++c) Pn[r][c] = wP.template load<HAUX>(r * NX + c);
+            FK_UNROLL for (int c = 0; c < NX; ++c) Pn[r][c] = ho.P.template load<HAUX>(r * NX + c);
     } else if (a.cont) {
         // a later chunk of the call: step T-1 of this window was smoothed by the chunk that ran before (after it in time)
         const MlView vx(a.xs + (T - 1) * xs_blk, t8, estride), vP(a.Ps_out + (T - 1) * ps_blk, off_rows, estride);
@@ -1001,31 +961,21 @@ rts_ml_kernel(const RtsArgs a_in)
             FK_UNROLL for (int c = 0; c < NX; ++c) fin = fin && (fabs(Pn[r][c]) <= 1.79769313486231570815e+308);
         int s = st | (fin ? 0 : ST_NONFINITE);
         s |= __builtin_amdgcn_mov_dpp(s, 0x55 * 1, 0xf, 0xf, true) | __builtin_amdgcn_mov_dpp(s, 0x55 * 2, 0xf, 0xf, true);
-        if constexpr (PERS) {
-            if (L == 0) {
-                const int old = a.status_or ? __hip_atomic_load(&a.status[trk], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-                __hip_atomic_store(&a.status[trk], old | s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        } else {
-            if (L == 0) a.status[trk] = a.status_or ? (a.status[trk] | s) : s;
+        if (L == 0) {
+            if constexpr (PERS) status_merge_agent(a.status, trk, a.status_or, s);
+            else a.status[trk] = a.status_or ? (a.status[trk] | s) : s;
         }
     }
     if constexpr (PERS) {
         if (pers_c + 1 < a_in.pers_H) {
             // not the group's last ticket: the smoothed state of this window's first step goes to the hand-over block
-            const unsigned n8 = (unsigned)N * 8u;
-            const MlView wx(a_in.pers_ws, (unsigned)trk * 8u, n8), wP(a_in.pers_ws + (long)NX * N, (unsigned)trk * 8u + Lc * (unsigned)(R * NX) * n8, n8);
-            FK_UNROLL for (int k = 0; k < NX; ++k) wx.template store<HAUX>(k, xn[k]);
+            const MlHandover<R, NX> ho(a_in.pers_ws, N, trk, Lc);
+            FK_UNROLL for (int k = 0; k < NX; ++k) ho.x.template store<HAUX>(k, xn[k]);
             FK_UNROLL for (int r = 0; r < R; ++r)
-                FK_UNROLL for (int c = 0; c < NX; ++c) wP.template store<HAUX>(r * NX + c, Pn[r][c]);
+                FK_UNROLL for (int c = 0; c < NX; ++c) ho.P.template store<HAUX>(r * NX + c, Pn[r][c]);
         }
-        // (complete only once every wave's vmcnt has drained: see kf_ml_kernel)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_store(&a_in.pers_ctl[1 + pers_g], pers_c + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-        break;
-    }
+        ticket_publish(a_in.pers_ctl, pers_g, pers_c + 1);
+    } else break;
     }      // tickets
 }
 
@@ -1043,46 +993,24 @@ static int launch_rts_ml_one(const RtsArgs &a, int layout, hipStream_t s)
 
 static int launch_rts_ml_chunked(const RtsArgs &a, int layout, hipStream_t s);
 
-// The smoother on the persistent grid (rts_ml_kernel<..., PERS>): same conditions, same scratch allocation scheme and the same
-// chunk count as launch_kf_ml_persistent below.  OFF unless FK_RTS_PERSIST=1: measured at configs[2] (1e5 tracks x 100 steps,
-// one lease, A/B/A/B): single launch 5.51 / 5.51 ms, tickets 5.51 / 5.61 (H = 3), 5.54 (2), 5.43 (4) -- nothing, where the forward
-// kernel gained 3-7 % (profiles/r06/c3_rts_persist.txt).  The smoother's fourth round of workgroups is as empty as the forward
-// kernel's, but its step is twice as long on the memory side (2736 against 1464 bytes per track-step): the three full rounds
-// already keep the memory system as busy as this kernel can.  Kept for the bit-identity test and the next idea.  FK_RTS_PERSIST_H: chunks.
+// The smoother on the persistent grid (rts_ml_kernel<..., PERS>; RTS_TICKETS, fk_tickets.hpp).  OFF unless FK_RTS_PERSIST is set and
+// not 0: at configs[2] single launch 5.51 / 5.51 ms, tickets 5.51 / 5.61 (H = 3), 5.54 (2), 5.43 (4) -- nothing, where the forward kernel
+// gained 3-7 % (profiles/r06/c3_rts_persist.txt, docs/KERNEL_NOTES.md).  Kept for the bit-identity test.  FK_RTS_PERSIST_H: chunks.
 static int launch_rts_ml_persistent(const RtsArgs &a, int layout, hipStream_t s)
 {
-    const char *pv = getenv("FK_RTS_PERSIST");
-    if (!pv || atoi(pv) == 0) return 1;
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                   ? prop.multiProcessorCount : 256;
-    }
-    const long cnt = a.cnt ? a.cnt : a.N;
-    const long G = (cnt + BLOCK / 4 - 1) / (BLOCK / 4), slots = 2L * n_cu;
-    long H = a.T >= 48 ? 3 : a.T / 16;
-    if (const char *hv = getenv("FK_RTS_PERSIST_H")) H = atol(hv);
-    if (G <= slots || H < 2 || a.T / H < 2 || G > (1L << 24)) return 1;
-    int *ctl = nullptr;
-    const size_t cbytes = ((size_t)(1 + G) * sizeof(int) + 255) & ~(size_t)255, wbytes = (size_t)90 * (size_t)a.N * sizeof(double);
-    if (hipMallocAsync((void **)&ctl, cbytes + wbytes, s) != hipSuccess || !ctl) { (void)hipGetLastError(); return 1; }
-    if (hipMemsetAsync(ctl, 0, cbytes, s) != hipSuccess) { (void)hipFreeAsync(ctl, s); (void)hipGetLastError(); return 1; }
+    const TicketPlan plan = ticket_plan(RTS_TICKETS, a.i0, a.cnt, a.N, a.T, cu_count);
+    const TicketScratch scratch(plan, s);
+    if (!scratch) return 1;                                    // not a call the grid takes (or no scratch)
     RtsArgs b = a;
-    b.pers_ctl = ctl;
-    b.pers_ws = reinterpret_cast<double *>(reinterpret_cast<char *>(ctl) + cbytes);
-    b.pers_G = (int)G;
-    b.pers_H = (int)H;
-    const dim3 grid((unsigned)slots), block(BLOCK);
+    b.pers_ctl = scratch.ctl, b.pers_ws = scratch.ws, b.pers_G = plan.G, b.pers_H = plan.H;
+    const dim3 grid(plan.grid), block(BLOCK);
+    const long cnt = a.cnt ? a.cnt : a.N;
     const char *pp = getenv("FK_ML_PAIRS");
     const bool pairs = (a.N % 2 == 0) && (cnt % 2 == 0) && cnt >= 2 && !(pp && atoi(pp) == 0);
     if (layout == FK_LAYOUT_AOS) hipLaunchKernelGGL((rts_ml_kernel<3, FK_ML_WAVES, 2, true>), grid, block, 0, s, b);
     else if (pairs) hipLaunchKernelGGL((rts_ml_kernel<3, FK_ML_WAVES, 1, true>), grid, block, 0, s, b);
     else hipLaunchKernelGGL((rts_ml_kernel<3, FK_ML_WAVES, 0, true>), grid, block, 0, s, b);
-    const int rc = check_launch("rts_ml_kernel<pers>");
-    (void)hipFreeAsync(ctl, s);
-    return rc;
+    return check_launch("rts_ml_kernel<pers>");
 }
 
 // returns 1 when this call is not one the multi-lane smoother serves
@@ -1120,49 +1048,23 @@ int launch_kf_ml_9_3(const KfArgs &a, int layout, bool outs, int model_mode, hip
     return launch_kf_ml_chunked(a, layout, outs, s);
 }
 
-// The persistent grid (PERS instantiations): where the bank is more workgroups than the chip holds at once and long enough
-// to cut -- G = ceil(cnt / 64) track groups x H time chunks of >= 16 steps, 2 workgroups per CU drawing tickets.  The
-// ticket counter and the G completion words live in a stream-ordered scratch allocation of this call (hipMallocAsync: no
-// state shared between concurrent calls; capturable).  FK_ML_PERSIST=0: off (the multi-stream tail filling below).
+// The persistent grid (PERS instantiations; KF_TICKETS, fk_tickets.hpp): where the bank is more workgroups than the chip holds at once
+// and long enough to cut into chunks of >= 16 steps.  FK_ML_PERSIST=0: off (the multi-stream tail filling below).
 static int launch_kf_ml_persistent(const KfArgs &a, int layout, bool outs, hipStream_t s)
 {
-    const char *pv = getenv("FK_ML_PERSIST");
-    if (pv && atoi(pv) == 0) return 1;
-    const char *sv = getenv("FK_ML_SLAB");
-    const bool slab = !(sv && atoi(sv) == 0);
-    if (!outs || (layout != FK_LAYOUT_AOS && !slab)) return 1;
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                   ? prop.multiProcessorCount : 256;
-    }
-    const long G = (a.cnt + BLOCK / 4 - 1) / (BLOCK / 4), slots = 2L * n_cu;
-    // chunks: more of them shorten the tail (ceil(G H / slots) rounds of T / H steps) but each costs a state reload and a
-    // pipeline start -- three measured best at configs[2] (3.10 ms; 4: 3.15, 6: 3.22, 10: 3.29; one launch 3.39)
-    long H = a.T >= 48 ? 3 : a.T / 16;
-    if (const char *hv = getenv("FK_ML_PERSIST_H")) H = atol(hv);
-    if (G <= slots || H < 2 || G > (1L << 24)) return 1;
-    int *ctl = nullptr;
-    const size_t cbytes = ((size_t)(1 + G) * sizeof(int) + 255) & ~(size_t)255, wbytes = (size_t)90 * (size_t)a.N * sizeof(double);
-    if (hipMallocAsync((void **)&ctl, cbytes + wbytes, s) != hipSuccess || !ctl) { (void)hipGetLastError(); return 1; }
-    if (hipMemsetAsync(ctl, 0, cbytes, s) != hipSuccess) { (void)hipFreeAsync(ctl, s); (void)hipGetLastError(); return 1; }
+    const TicketPlan plan = ticket_plan(KF_TICKETS, a.i0, a.cnt, a.N, a.T, cu_count, kf_tickets_serve(outs, layout == FK_LAYOUT_AOS));
+    const TicketScratch scratch(plan, s);
+    if (!scratch) return 1;                                    // not a call the grid takes (or no scratch)
     KfArgs b = a;
-    b.pers_ctl = ctl;
-    b.pers_ws = reinterpret_cast<double *>(reinterpret_cast<char *>(ctl) + cbytes);
-    b.pers_G = (int)G;
-    b.pers_H = (int)H;
-    const dim3 grid((unsigned)slots), block(BLOCK);
+    b.pers_ctl = scratch.ctl, b.pers_ws = scratch.ws, b.pers_G = plan.G, b.pers_H = plan.H;
+    const dim3 grid(plan.grid), block(BLOCK);
 #define GOP(M)                                                                                                              \
     if (layout == FK_LAYOUT_AOS)                                                                                            \
         hipLaunchKernelGGL((kf_ml_kernel<3, 3, true, FK_ML_WAVES, false, M, LAYOUT_AOS, false, false, false, true>), grid, block, 0, s, b); \
     else hipLaunchKernelGGL((kf_ml_kernel<3, 3, true, FK_ML_WAVES, false, M, LAYOUT_SOA, false, false, true, true>), grid, block, 0, s, b)
     if (a.mask) { GOP(true); } else { GOP(false); }
 #undef GOP
-    const int rc = check_launch("kf_ml_kernel<pers>");
-    (void)hipFreeAsync(ctl, s);
-    return rc;
+    return check_launch("kf_ml_kernel<pers>");
 }
 
 // one launch over tracks [a.i0, a.i0 + a.cnt), a.T steps from the pointers in `a`
@@ -1191,14 +1093,8 @@ static int launch_kf_ml_one(const KfArgs &a, int layout, bool outs, hipStream_t 
     return check_launch("kf_ml_kernel");
 }
 
-// Tail filling.  The step is bound by arithmetic and latency, every wave runs the same T steps, so a bank of W waves on S
-// wave slots takes ceil(W / S) rounds: BASELINE config 3 (1e5 tracks = 6250 waves on 2048 slots) pays 4 rounds for 3.05
-// rounds of work.  A chunked call cuts the bank into G track groups (multiples of 64 tracks) and the T steps into H time
-// chunks and launches the G x H pieces on G streams -- group g's chunks in order on stream g, the state handed from chunk
-// to chunk through x / P in place (kernel boundaries of one stream: no protocol), different groups concurrently: while one
-// group's piece tails off, the other groups' pieces fill the slots, and what is left at the very end is the tail of a
-// piece 1/H as long.  Same arithmetic per track: results are bit-identical to the single launch.  The helper streams
-// fork from and join the caller's stream with events (capturable); they and the events are created once.
+// Tail filling where the persistent grid does not take the call: G track groups x H time chunks as pieces on G streams
+// (fk_chunk_plan.hpp: the policy, the pieces and the driver; fk_chunks.hpp: the streams).  Bit-identical to the single launch.
 static int launch_rts_ml_chunked(const RtsArgs &a, int layout, hipStream_t s)
 {
     return rts_chunked_call(a, 9, 2048, [layout](const RtsArgs &b, hipStream_t sb) { return launch_rts_ml_one(b, layout, sb); }, s);

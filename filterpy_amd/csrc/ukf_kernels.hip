@@ -23,6 +23,7 @@
 #include "fk_kernel_args.hpp"
 #include "fk_launchers.hpp"
 #include "fk_math_sym.hpp"
+#include "fk_tickets.hpp"
 #include "fk_ukf.hpp"
 
 namespace fk {
@@ -63,14 +64,9 @@ namespace fk {
 //     each (wave_store_soa_pairs: 21 instead of 42 vector-memory operations per step at (6,3)).  Compile-time, not a branch:
 //     two store sequences of different lengths behind a run-time test make the compiler's s_waitcnt for z a vmcnt(0).
 //     Full workgroups only -- the launcher hands the last partial workgroup to the plain instantiation.
-//   * PERS (round 6): a persistent grid drawing TICKETS, like kf_ml's (kf_ml.hip).  Every wave runs the same T steps, and BASELINE
-//     configs[3] is 391 workgroups for 512 slots (two per CU): 135 CUs carry two workgroups for the whole call, 121 carry one
-//     and idle half their issue slots -- the launch takes what a two-workgroup CU takes (round 5: VALU executing 32 % of wave
-//     residency, 49 % waiting for issue).  Here the call is cut into G = ceil(N / 256) track groups x H time chunks and 2 x CUs
-//     resident workgroups draw tickets chunk-major; chunk h of a group waits for chunk h - 1 (a ticket at least G draws older:
-//     held by a workgroup that runs or is done) through a completion word and picks the state up from an element-major
-//     hand-over block ([NX + NX (NX + 1) / 2][N], agent-scope accesses: no fence, no L2 write-back).  Same arithmetic per
-//     track: bit-identical to the single launch (tests/test_gpu_ukf.py).
+//   * PERS (round 6): a persistent ticket grid like kf_ml's (fk_tickets.hpp).  BASELINE configs[3] is 391 workgroups for 512 slots: 135 CUs
+//     carry two workgroups for the whole call, 121 carry one and idle half their issue slots.  Here G = ceil(N / 256) track groups x H time chunks
+//     are drawn by 2 x CUs resident workgroups; hand-over block [NX + NX (NX + 1) / 2][N], element-major.  Bit-identical to the single launch.
 template <int NX, int NZ, int LAYOUT, bool EXACT, bool PAIRED, bool SP = false, bool PERS = false>
 __global__ void __launch_bounds__(BLOCK, (NX <= 2 ? 4 : NX <= 6 ? 2 : 1))
 ukf_linear_kernel(const UkfArgs a_in, const double *__restrict__ pF, const double *__restrict__ pH,
@@ -143,29 +139,21 @@ ukf_linear_kernel(const UkfArgs a_in, const double *__restrict__ pF, const doubl
     for (;;) {                                                   // PERS: one trip per ticket; otherwise exactly one trip
     unsigned bid = blockIdx.x;
     if constexpr (PERS) {
-        __syncthreads();                                         // the previous ticket's LDS traffic is over, s_task is free
-        if (threadIdx.x == 0) s_task = atomicAdd(pers_ctl, 1);
-        __syncthreads();
-        const int task = __builtin_amdgcn_readfirstlane(s_task);
+        const int task = ticket_draw(pers_ctl, s_task);
         if (task >= pers_G * pers_H) break;
-        pers_h = task / pers_G;
-        pers_g = task - pers_h * pers_G;
+        const TicketWindow w = ticket_window(task, pers_G, pers_H, a_in.T, false);
+        pers_h = w.chunk, pers_g = w.g;
         bid = (unsigned)pers_g;
-        const long t0 = a_in.T * pers_h / pers_H, t1 = a_in.T * (pers_h + 1) / pers_H;
+        const long t0 = w.t0;
         a = a_in;
-        a.T = t1 - t0;
+        a.T = w.t1 - t0;
         pz = pz_in + t0 * N * m;
         pmask = pmask_in ? pmask_in + t0 * N : nullptr;
         a.means = a_in.means ? a_in.means + t0 * N * NX : nullptr;
         a.covs = a_in.covs ? a_in.covs + t0 * N * (NX * NX) : nullptr;
         a.status_or = t0 > 0 ? 1 : a_in.status_or;
         st = st_prologue;
-        if (pers_h > 0) {
-            if (threadIdx.x == 0) {
-                while (__hip_atomic_load(&pers_ctl[1 + pers_g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < pers_h) __builtin_amdgcn_s_sleep(8);
-            }
-            __syncthreads();
-        }
+        ticket_wait(pers_ctl, pers_g, pers_h);
     }
     const long blk0 = a.i0 + (long)bid * BLOCK;
     const long left = a.i0 + a.cnt - blk0;
@@ -264,23 +252,12 @@ ukf_linear_kernel(const UkfArgs a_in, const double *__restrict__ pF, const doubl
         }
         if (a.status) {
             if (!all_finite<NX>(x) || !all_finite<PL>(P)) st |= ST_NONFINITE;
-            if constexpr (PERS) {
-                const int old = a.status_or ? __hip_atomic_load(&a.status[ln.blk0 + ln.tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-                __hip_atomic_store(&a.status[ln.blk0 + ln.tid], old | st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-                a.status[ln.blk0 + ln.tid] = a.status_or ? (a.status[ln.blk0 + ln.tid] | st) : st;
-            }
+            if constexpr (PERS) status_merge_agent(a.status + ln.blk0, ln.tid, a.status_or, st);
+            else a.status[ln.blk0 + ln.tid] = a.status_or ? (a.status[ln.blk0 + ln.tid] | st) : st;
         }
     }
-    if constexpr (PERS) {
-        // the chunk's state (and status) is in place once every wave's vmcnt has drained -- a workgroup barrier does not wait
-        // for VMEM (kf_ml.hip) --, then the barrier, then the chunk is published
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_store(&pers_ctl[1 + pers_g], pers_h + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-        break;
-    }
+    if constexpr (!PERS) break;
+    else ticket_publish(pers_ctl, pers_g, pers_h + 1);           // the chunk's state (and status) is in place
     }      // tickets
 }
 
@@ -322,58 +299,26 @@ static void ukf_launch_sp(const UkfArgs &a, hipStream_t s)
     }
 }
 
-// The persistent grid (PERS instantiation; the exact (6, 3) class with pair weights: BASELINE configs[3]): a whole-bank call of
-// more workgroups than CUs and at least 32 steps is cut into G track groups x H time chunks, 2 x CUs resident workgroups draw
-// tickets.  H: the count in [4, T / 6] whose last round of tickets is fullest (ceil(G H / slots) rounds of T / H steps), the
-// larger chunk on a draw.  The ticket counter, the completion words and the hand-over block live in a stream-ordered scratch
-// allocation of this call (hipMallocAsync: no state shared between concurrent calls).  FK_UKF_PERSIST=0: off;
-// FK_UKF_PERSIST_H: the chunk count.  Returns 1 where the call is not one it takes.
+// The persistent grid (PERS instantiation; the exact (6, 3) class with pair weights: BASELINE configs[3]; UKF_TICKETS, fk_tickets.hpp).
+// OFF unless FK_UKF_PERSIST=1: one launch 0.81-0.85 ms, H = 5 / 8 / 10 / 13 chunks 0.87 / 0.91 / 0.94 / 0.96 -- bound by ONE wave's dependent
+// instruction chain, not by the spread of the waves (docs/KERNEL_NOTES.md).  FK_UKF_PERSIST_H: chunks.  Returns 1 where it does not take the call.
 template <bool PV>
 static int ukf_fwd_persistent_6_3(const UkfArgs &a, int layout, hipStream_t s)
 {
     if constexpr (!PV) return 1;
     else {
-    // OFF unless FK_UKF_PERSIST=1.  Measured (profiles/r06/ukf_persist.txt, 1e5 x 100, same lease): one launch 0.81-0.85 ms, tickets
-    // with H = 5 / 8 / 10 / 13 chunks 0.87 / 0.91 / 0.94 / 0.96 -- every chunk costs ~10 us (ticket, completion word, state reload,
-    // drain) and the balance buys NOTHING: a CU that carries one workgroup takes as long as one that carries two.  The launch is
-    // bound by the length of ONE wave's dependent instruction chain (100 steps x 1193 instructions at ~6.9 ns each), not by issue
-    // slots: what would help is a shorter chain per step, not a better spread of the waves.
-    const char *pv = getenv("FK_UKF_PERSIST");
-    if (!(pv && atoi(pv) == 1)) return 1;
-    if (a.i0 != 0 || a.cnt != a.N || a.T < 32) return 1;
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                   ? prop.multiProcessorCount : 256;
-    }
-    const long G = (a.cnt + BLOCK - 1) / BLOCK, slots = 2L * n_cu;
-    if (G <= n_cu || G > (1L << 24)) return 1;
-    long H = 0;
-    double best = 0.0;
-    for (long h = 4; h <= a.T / 6; ++h) {
-        const double rounds = (double)(G * h) / (double)slots, fill = rounds / (double)((G * h + slots - 1) / slots);
-        if (fill > best + 0.02) { best = fill; H = h; }
-    }
-    if (const char *hv = getenv("FK_UKF_PERSIST_H")) H = atol(hv);
-    if (H < 2 || H > a.T) return 1;
-    const bool sp = layout == FK_LAYOUT_SOA && ukf_sp_ok<6>(a);
-    int *ctl = nullptr;
-    const size_t cbytes = ((size_t)(1 + G) * sizeof(int) + 255) & ~(size_t)255, wbytes = (size_t)(6 + 21) * (size_t)a.N * sizeof(double);
-    if (hipMallocAsync((void **)&ctl, cbytes + wbytes, s) != hipSuccess || !ctl) { (void)hipGetLastError(); return 1; }
-    if (hipMemsetAsync(ctl, 0, cbytes, s) != hipSuccess) { (void)hipFreeAsync(ctl, s); (void)hipGetLastError(); return 1; }
-    double *ws = reinterpret_cast<double *>(reinterpret_cast<char *>(ctl) + cbytes);
-    const dim3 grid((unsigned)(G * H < slots ? G * H : slots)), block(BLOCK);
-    if (layout == FK_LAYOUT_SOA) {
-        if (sp) hipLaunchKernelGGL((ukf_linear_kernel<6, 3, LAYOUT_SOA, true, true, true, true>), grid, block, 0, s, a, a.F, a.H, a.Q, a.R, a.Wm, a.Wc, a.z, a.mask, ctl, ws, (int)G, (int)H);
-        else hipLaunchKernelGGL((ukf_linear_kernel<6, 3, LAYOUT_SOA, true, true, false, true>), grid, block, 0, s, a, a.F, a.H, a.Q, a.R, a.Wm, a.Wc, a.z, a.mask, ctl, ws, (int)G, (int)H);
-    } else {
-        hipLaunchKernelGGL((ukf_linear_kernel<6, 3, LAYOUT_AOS, true, true, false, true>), grid, block, 0, s, a, a.F, a.H, a.Q, a.R, a.Wm, a.Wc, a.z, a.mask, ctl, ws, (int)G, (int)H);
-    }
-    const int rc = check_launch("ukf_linear_kernel<pers>");
-    (void)hipFreeAsync(ctl, s);
-    return rc;
+    const TicketPlan plan = ticket_plan(UKF_TICKETS, a.i0, a.cnt, a.N, a.T, cu_count);
+    const TicketScratch scratch(plan, s);
+    if (!scratch) return 1;                                    // not a call the grid takes (or no scratch)
+    const dim3 grid(plan.grid), block(BLOCK);
+#define FK_UKF_TICKETS(LAY, SPV)                                                                                          \
+    hipLaunchKernelGGL((ukf_linear_kernel<6, 3, LAY, true, true, SPV, true>), grid, block, 0, s, a, a.F, a.H, a.Q, a.R, a.Wm, a.Wc, \
+                       a.z, a.mask, scratch.ctl, scratch.ws, plan.G, plan.H)
+    if (layout != FK_LAYOUT_SOA) FK_UKF_TICKETS(LAYOUT_AOS, false);
+    else if (ukf_sp_ok<6>(a)) FK_UKF_TICKETS(LAYOUT_SOA, true);
+    else FK_UKF_TICKETS(LAYOUT_SOA, false);
+#undef FK_UKF_TICKETS
+    return check_launch("ukf_linear_kernel<pers>");
     }
 }
 

@@ -806,3 +806,30 @@ extern "C" long hc_chunk_trace(int family, const long *cfg, unsigned null, long 
     if (cap > 0) out[0] = rc;
     return tr.n;
 }
+
+
+// ---------------------------------------------------------------------------------------------------------
+// The persistent ticket grids (filterpy_amd/csrc/fk_tickets.hpp, part 1: what the launchers of kf_ml.hip and ukf_kernels.hip
+// ask before they allocate and launch, and the split of a ticket that their kernels run).
+#include "../../filterpy_amd/csrc/fk_tickets.hpp"
+
+// family: 0 kf_ml_kernel, 1 rts_ml_kernel, 2 ukf_linear_kernel (6,3); outs / aos: what the forward filter's call has (family 0).
+// out: take, G, H, grid, ctl_bytes, ws_bytes.  The switches are read from the environment, as in the library.
+extern "C" int hc_ticket_plan(int family, long i0, long cnt, long N, long T, int n_cu, int outs, int aos, long *out)
+{
+    const fk::TicketPolicy *pol[3] = {&fk::KF_TICKETS, &fk::RTS_TICKETS, &fk::UKF_TICKETS};
+    if (family < 0 || family > 2) return -1;
+    const fk::TicketPlan p = fk::ticket_plan(*pol[family], i0, cnt, N, T, [n_cu] { return n_cu; },
+                                             family != 0 || fk::kf_tickets_serve(outs != 0, aos != 0));
+    out[0] = p.take, out[1] = p.G, out[2] = p.H, out[3] = p.grid, out[4] = (long)p.ctl_bytes, out[5] = (long)p.ws_bytes;
+    return p.take;
+}
+
+// tickets 0 .. G H - 1 in drawing order; out: [G H][g, chunk, t0, t1, cont]
+extern "C" void hc_ticket_windows(int G, int H, long T, int backward, long *out)
+{
+    for (int task = 0; task < G * H; ++task, out += 5) {
+        const fk::TicketWindow w = fk::ticket_window(task, G, H, T, backward != 0);
+        out[0] = w.g, out[1] = w.chunk, out[2] = w.t0, out[3] = w.t1, out[4] = w.cont;
+    }
+}
