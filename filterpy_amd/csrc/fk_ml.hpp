@@ -1,8 +1,18 @@
-// fk_ml.hpp -- cross-lane and buffer-access helpers shared by the several-lanes-per-track kernels
-// (kf_ml.hip: dim_x = 9 on three lanes; kf_mlg.hip: dim_x 10..16 on four lanes).
+// fk_ml.hpp -- the exchange layer of the several-lanes-per-track kernels: cross-lane moves, buffer access and the copy-outs
+// through a wave's LDS tile.  Its six users:
+//   kf_ml.hip    KalmanFilter.batch_filter / rts_smoother, dim_x = 9 on three lanes   (LaneGroup<3>)
+//   kf_mlg.hip   batch_filter, dim_x 10..16 on four lanes                               (LaneGroup<4>)
+//   rts_mlg.hip  rts_smoother, dim_x 8..16 on four lanes                                (LaneGroup<4>)
+//   rts_mlx.hip  rts_smoother, dim_x 15, 16 on eight lanes, rows exchanged through LDS  (LaneGroup<8>: the status merge only)
+//   imm_quad.hip IMM / MMAE banks, four or eight lanes per filter                       (LaneGroup<4>, LaneGroup<8>)
+//   ukf_mlg.hip  the fused linear UKF and its smoother, four or eight lanes             (LaneGroup<4>, LaneGroup<8>)
+// (imm_lanes.hip takes ml_wave_fence only.)  An exchange between the lanes of a group is DEFINED here -- LaneGroup -- and none of
+// the six holds a cross-lane builtin of its own; "row k's owner's value" on top of it is fk_owner.hpp's ladder (one ladder stays
+// written in place, over LaneGroup::bcast, in rts_mlg.hip).  docs/KERNEL_NOTES.md says what a new family may assume and why.
 #pragma once
 #include <type_traits>
 #include "fk_device.hpp"
+#include "fk_owner.hpp"
 
 // element-major covariances of the four-lane kernels leave through the LDS slab (ml_store_rows_soa_slab) up to this dim_x;
 // above it: 8-byte stores per lane.  (Round 2 measured the slab as a loss above 12 -- with a copy-out that cost a division,
@@ -40,6 +50,93 @@ __device__ __forceinline__ double quad_rot(double v)
     hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
     return __hiloint2double(hi, lo);
 }
+
+// FK_UMLG_OCT_DPP=0 (build-time A/B, measured in ukf_mlg.hip's eight-lane kernels): LaneGroup<8>::bcast through ds_swizzle's bit mode
+// instead of the VALU -- within every group of 32 lanes the source lane is ((lane & and_mask) | or_mask) ^ xor_mask: and 0x18 keeps
+// the group of eight, or O picks its lane O (the assembler prints these as swizzle(BROADCAST,8,O)).  The LDS crossbar, no memory
+// access; two per double on the LDS pipe against four VALU moves: the eight-lane kernels kept the LDS pipe of a CU busy in 80 % of
+// the cycles (four waves x 20 %, profiles/r06/ukf_mlg_counters/) with the VALU at 35 %.  The same bits either way.
+#ifndef FK_UMLG_OCT_DPP
+#define FK_UMLG_OCT_DPP 1
+#endif
+
+// The LPT adjacent lanes that share a track (or a filter): a quad (3: its lane 3 mirrors lane 2) or 8 = a pair of quads inside a
+// DPP row of 16.
+// Stateless; every member is a fixed instruction sequence.
+template <int LPT>
+struct LaneGroup {
+    static_assert(LPT == 3 || LPT == 4 || LPT == 8, "three, four or eight lanes per track");
+    static constexpr int LANES = LPT;
+    // The value lane O of the group holds, in every lane of it.  Within a quad: one quad-permute move per half.  Eight lanes: DPP
+    // cannot leave a quad, so every quad broadcasts ITS lane O % 4, then the quad of the pair that does not hold lane O takes the
+    // other quad's value -- row_shr:4 into the odd quads (bank mask 0xA) or row_shl:4 into the even ones (0x5).
+    template <int O>
+    static __device__ __forceinline__ double bcast(double v)
+    {
+        static_assert(O >= 0 && O < LPT, "a lane of the group");
+        if constexpr (LPT <= 4) {
+            return quad_bcast<O>(v);
+        } else {
+#if FK_UMLG_OCT_DPP
+            constexpr int q = O & 3, ctrl = (O >> 2) == 0 ? 0x114 : 0x104, banks = (O >> 2) == 0 ? 0xA : 0x5;
+            int lo = __double2loint(v), hi = __double2hiint(v);
+            lo = __builtin_amdgcn_mov_dpp(lo, q * 0x55, 0xf, 0xf, true);
+            hi = __builtin_amdgcn_mov_dpp(hi, q * 0x55, 0xf, 0xf, true);
+            lo = __builtin_amdgcn_update_dpp(lo, lo, ctrl, 0xf, banks, false);
+            hi = __builtin_amdgcn_update_dpp(hi, hi, ctrl, 0xf, banks, false);
+#else
+            constexpr int pat = 0x18 | (O << 5);
+            const int lo = __builtin_amdgcn_ds_swizzle(__double2loint(v), pat), hi = __builtin_amdgcn_ds_swizzle(__double2hiint(v), pat);
+#endif
+            return __hiloint2double(hi, lo);
+        }
+    }
+    // The sum of a value over the group, the same bits in every lane of it.  The ASSOCIATION is part of the contract (the
+    // bit-identity and precision tests rest on it):
+    //   4: (a0 + a1) + (a2 + a3) in lanes 0, 1 and (a2 + a3) + (a0 + a1) in lanes 2, 3 (fp addition commutes);
+    //   8: the quad's sum as above, plus the other quad's (row_shr:4 / row_shl:4 with the bank masks of bcast);
+    //   3: (a_L + a_{L+1}) + a_{L+2}, indices mod 3 (the mirror lane: (a2 + a0) + a1).
+    static __device__ __forceinline__ double sum(double v)
+    {
+        if constexpr (LPT == 3) {
+            return (v + quad_rot<0x09>(v)) + quad_rot<0x52>(v);     // quad_perm:[1,2,0,0], [2,0,1,1]
+        } else {
+            v += quad_rot<0xB1>(v);      // quad_perm:[1,0,3,2]
+            v += quad_rot<0x4E>(v);      // quad_perm:[2,3,0,1]
+            if constexpr (LPT == 8) {
+                const int lo = __double2loint(v), hi = __double2hiint(v);
+                int plo = __builtin_amdgcn_update_dpp(lo, lo, 0x114, 0xf, 0xA, false);
+                int phi = __builtin_amdgcn_update_dpp(hi, hi, 0x114, 0xf, 0xA, false);
+                plo = __builtin_amdgcn_update_dpp(plo, lo, 0x104, 0xf, 0x5, false);
+                phi = __builtin_amdgcn_update_dpp(phi, hi, 0x104, 0xf, 0x5, false);
+                v += __hiloint2double(phi, plo);
+            }
+            return v;
+        }
+    }
+    // The OR of a status word over the group, IN EVERY LANE of it (four lanes: two quad-permute steps)
+    static __device__ __forceinline__ int any(int s)
+    {
+        static_assert(LPT == 4, "three and eight lanes: any_lane0");
+        s |= __builtin_amdgcn_mov_dpp(s, 0xB1, 0xf, 0xf, true);
+        s |= __builtin_amdgcn_mov_dpp(s, 0x4E, 0xf, 0xf, true);
+        return s;
+    }
+    // ... guaranteed IN LANE 0 of the group only, which writes it (four lanes: any()).  Three lanes: lanes 1 and 2 broadcast (the
+    // other lanes end up without lane 0's bits).  Eight: the two steps of any(), then row_shl:4 -- lanes 0..3 of the group see
+    // lanes 4..7, which in turn see the NEXT group's.
+    static __device__ __forceinline__ int any_lane0(int s)
+    {
+        if constexpr (LPT == 3) {
+            s |= __builtin_amdgcn_mov_dpp(s, 0x55 * 1, 0xf, 0xf, true) | __builtin_amdgcn_mov_dpp(s, 0x55 * 2, 0xf, 0xf, true);
+        } else {
+            s |= __builtin_amdgcn_mov_dpp(s, 0xB1, 0xf, 0xf, true);
+            s |= __builtin_amdgcn_mov_dpp(s, 0x4E, 0xf, 0xf, true);
+            if constexpr (LPT == 8) s |= __builtin_amdgcn_mov_dpp(s, 0x104, 0xf, 0xf, true);
+        }
+        return s;
+    }
+};
 
 // A buffer store of more than 8 bytes reads its data registers over several cycles; the VALU must not overwrite
 // them in the next cycle.  hipcc keeps that distance itself -- except when the store's soffset is an SGPR, which the
@@ -277,6 +374,24 @@ __device__ __forceinline__ void ml_tile_out_aos(double *dst, const double *tile,
                         [&](unsigned unit, bool ok, const u32x4 &v) {
                             __builtin_amdgcn_raw_buffer_store_b128(v, rs, ok ? unit * 16u : ML_OFF_DROP, 0, 0);
                         });
+}
+
+// AOS ([track][element], NumPy order) output of one row-block matrix of a wave's TPW consecutive tracks -- the twin of
+// ml_store_rows_soa_slab: the lanes write their rows into the wave-private tile laid out like the wave's slab, then ml_tile_out_aos.
+//   dst: record of the wave's first track.  The lane's track within the wave is formed HERE, not passed like the twin's g: handed
+//   over as an argument it changed the schedule of the dim_x 8 smoother.  No fence behind the copy-out: a caller whose tile is a
+//   park that gets reused adds its own.
+template <int R, int NX, int TPW>
+__device__ __forceinline__ void ml_store_rows_aos(const double (&M)[R][NX], const unsigned (&row)[R], double *dst, double *tile,
+                                                  unsigned lane, unsigned valid)
+{
+    constexpr int EP = NX * NX;
+    const unsigned g = lane / (unsigned)(64 / TPW);
+    ml_wave_fence();
+    FK_UNROLL for (int r = 0; r < R; ++r)
+        FK_UNROLL for (int c = 0; c < NX; ++c) tile[g * EP + row[r] * NX + c] = M[r][c];
+    ml_wave_fence();
+    ml_tile_out_aos<EP, TPW>(dst, tile, lane, valid);
 }
 
 template <int E, int TPW>

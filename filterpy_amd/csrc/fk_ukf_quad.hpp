@@ -1,5 +1,5 @@
 // fk_ukf_quad.hpp -- one predict + update step of the fused linear-model UKF, and one backward step of its smoother, with SEVERAL
-// LANES PER TRACK (LN = 4: a quad, DPP exchanges; LN = 8: ds_swizzle) -- the arithmetic of ukf_mlg.hip (dim_x 10..16).
+// LANES PER TRACK (LN = 4: a quad; LN = 8: a pair of quads -- LaneGroup<LN> of fk_ml.hpp) -- the arithmetic of ukf_mlg.hip (dim_x 10..16).
 // __host__ __device__ like fk_ukf.hpp: the kernels run it with the exchanges as cross-lane moves, tests/hostcheck runs the very same
 // code on the host with the lanes of a track as fibers in lockstep (tests/test_hostcheck_ukf_quad.py).
 //
@@ -17,12 +17,14 @@
 //     owners), each lane accumulates its own rows;
 //   * dim_z <= 4: S, its L D L' and z - zp are replicated; the gain's rows are solved by their owners and gathered one at a time
 //     for x += K (z - zp) and P -= K (S K').  dim_z >= 5: S is distributed and factored like P, P -= W W' (see there).
-// The only exchange is "the value lane o of my group holds" (quad.bcast<o>(v)); there is no cross-lane sum.  A row of P computed
-// by one lane and its mirror image computed by another agree to a rounding (f_a (w f_b) against f_b (w f_a)), not bit for
-// bit; the factorisation reads a row's own elements.
+// The only exchange is "the value lane o of my group holds": owner_value<1, LN>(quad, o, v), fk_owner.hpp's ladder with one row per
+// rung (the rows are cyclic; o is a constant once the loops are unrolled, so one quad.bcast<o>(v) survives); there is no
+// cross-lane sum.  A row of P computed by one lane and its mirror image computed by another agree to a rounding (f_a (w f_b)
+// against f_b (w f_a)), not bit for bit; the factorisation reads a row's own elements.
 // A missing measurement runs the update half on z = 0 with the gain, S and the residual selected to zero (no branch).
 #pragma once
 
+#include "fk_owner.hpp"
 #include "fk_ukf.hpp"
 
 namespace fk {
@@ -30,24 +32,6 @@ namespace fk {
 struct UkfQuadModel {
     const double *F, *Q, *H, *R, *Wp;       // row-major [n][n], [n][n], [m][n], [m][m]; the pair table (make_pair_table)
 };
-
-// the value lane o of the track's lane group holds (o is a constant wherever this is used, once the loops are unrolled);
-// LN: lanes per track -- 4 (a quad: DPP) or 8 (the smoother at dim_x >= 13: half the unrolled arithmetic per lane)
-template <int LN = 4, class Quad>
-FK_HD double quad_from(Quad &quad, double v, int o)
-{
-    if (o == 0) return quad.template bcast<0>(v);
-    if (o == 1) return quad.template bcast<1>(v);
-    if (o == 2) return quad.template bcast<2>(v);
-    if constexpr (LN == 4) return quad.template bcast<3>(v);
-    else {
-        if (o == 3) return quad.template bcast<3>(v);
-        if (o == 4) return quad.template bcast<4>(v);
-        if (o == 5) return quad.template bcast<5>(v);
-        if (o == 6) return quad.template bcast<6>(v);
-        return quad.template bcast<7>(v);
-    }
-}
 
 // Lower factor of scale * P, rows distributed cyclically (g[r]: the row slot r holds -- q + LN r, clamped to NX - 1).
 // Lw[r][k], k <= LN r + LN - 1: the lane's rows (zero above the diagonal; entries past that are never written nor read).
@@ -64,13 +48,13 @@ FK_HD bool quad_chol_rows(const double (&P)[(NX + LN - 1) / LN][NX], const unsig
         double dl = scale * P[sj][j];
         FK_UNROLL for (int k = 0; k < NX; ++k)
             if (k < j) dl = fma(-Lw[sj][k], Lw[sj][k], dl);
-        const double d = quad_from<LN>(quad, dl, oj);
+        const double d = owner_value<1, LN>(quad, oj, dl);
         pd = pd && (d > 0.0);
         double ljj, inv;
         sqrt_rsqrt(d, ljj, inv);
         double lrow[NX];
         FK_UNROLL for (int k = 0; k < NX; ++k)
-            if (k < j) lrow[k] = quad_from<LN>(quad, Lw[sj][k], oj);
+            if (k < j) lrow[k] = owner_value<1, LN>(quad, oj, Lw[sj][k]);
         FK_UNROLL for (int r = 0; r < R; ++r) {
             if (LN * r + LN - 1 < j) continue;                      // the slot's rows all lie above row j
             double t = scale * P[r][j];
@@ -121,7 +105,7 @@ FK_HD int ukf_quad_step_v4(double (&x)[NX], double (&P)[(NX + LN - 1) / LN][NX],
         {
             double wy[NX];
             FK_UNROLL for (int b = 0; b < NX; ++b) {
-                const double fx = quad_from<LN>(quad, Fxo[b / LN], b % LN);
+                const double fx = owner_value<1, LN>(quad, b % LN, Fxo[b / LN]);
                 x[b] = wms * fx;
                 wy[b] = wcs * (fx - x[b]);
             }
@@ -137,7 +121,7 @@ FK_HD int ukf_quad_step_v4(double (&x)[NX], double (&P)[(NX + LN - 1) / LN][NX],
             const double wp = mv.Wp[2 + k];
             double wfo[R], wf[NX];
             FK_UNROLL for (int r = 0; r < R; ++r) wfo[r] = wp * FL[r][k];
-            FK_UNROLL for (int b = 0; b < NX; ++b) wf[b] = quad_from<LN>(quad, wfo[b / LN], b % LN);
+            FK_UNROLL for (int b = 0; b < NX; ++b) wf[b] = owner_value<1, LN>(quad, b % LN, wfo[b / LN]);
             FK_UNROLL for (int r = 0; r < R; ++r)
                 FK_UNROLL for (int b = 0; b < NX; ++b) P[r][b] = fma(FL[r][k], wf[b], P[r][b]);
             FK_STAGE();
@@ -214,7 +198,7 @@ FK_HD int ukf_quad_step_v4(double (&x)[NX], double (&P)[(NX + LN - 1) / LN][NX],
             FK_UNROLL for (int k = 0; k < NX; ++k) {
                 const double wp = mv.Wp[2 + k];
                 double wh[NZ];
-                FK_UNROLL for (int c = 0; c < NZ; ++c) wh[c] = wp * quad_from<LN>(quad, HLo[c / LN][k], c % LN);
+                FK_UNROLL for (int c = 0; c < NZ; ++c) wh[c] = wp * owner_value<1, LN>(quad, c % LN, HLo[c / LN][k]);
                 FK_UNROLL for (int rz = 0; rz < RZ; ++rz)
                     FK_UNROLL for (int c = 0; c < NZ; ++c) So[rz][c] = fma(HLo[rz][k], wh[c], So[rz][c]);
                 FK_UNROLL for (int r = 0; r < R; ++r) {
@@ -243,7 +227,7 @@ FK_HD int ukf_quad_step_v4(double (&x)[NX], double (&P)[(NX + LN - 1) / LN][NX],
             // P -= W W': row b of W from its owner
             FK_UNROLL for (int b = 0; b < NX; ++b) {
                 double Wb[NZ];
-                FK_UNROLL for (int c = 0; c < NZ; ++c) Wb[c] = quad_from<LN>(quad, Ko[(b / LN) * NZ + c], b % LN);
+                FK_UNROLL for (int c = 0; c < NZ; ++c) Wb[c] = owner_value<1, LN>(quad, b % LN, Ko[(b / LN) * NZ + c]);
                 FK_UNROLL for (int r = 0; r < R; ++r) {
                     double acc = Ko[r * NZ] * Wb[0];
                     FK_UNROLL for (int qq = 1; qq < NZ; ++qq) acc = fma(Ko[r * NZ + qq], Wb[qq], acc);
@@ -255,7 +239,7 @@ FK_HD int ukf_quad_step_v4(double (&x)[NX], double (&P)[(NX + LN - 1) / LN][NX],
             FK_UNROLL for (int i = NZ - 1; i >= 0; --i) {
                 double col[NZ];
                 FK_UNROLL for (int k = 0; k < NZ; ++k)
-                    if (k > i) col[k] = quad_from<LN>(quad, Ls[k / LN][i], k % LN);
+                    if (k > i) col[k] = owner_value<1, LN>(quad, k % LN, Ls[k / LN][i]);
                 FK_UNROLL for (int r = 0; r < R; ++r) {
                     double acc = Ko[r * NZ + i];
                     FK_UNROLL for (int k = NZ - 1; k >= 0; --k)
@@ -273,7 +257,7 @@ FK_HD int ukf_quad_step_v4(double (&x)[NX], double (&P)[(NX + LN - 1) / LN][NX],
                     FK_UNROLL for (int c = 1; c < NZ; ++c) acc = fma(Ko[r * NZ + c], zc[c], acc);
                     xo[r] = has_z ? acc : 0.0;
                 }
-                FK_UNROLL for (int b = 0; b < NX; ++b) x[b] += quad_from<LN>(quad, xo[b / LN], b % LN);
+                FK_UNROLL for (int b = 0; b < NX; ++b) x[b] += owner_value<1, LN>(quad, b % LN, xo[b / LN]);
             }
         } else {
             double zp[NZ], S[NZ * NZ], Ko[R * NZ];
@@ -295,7 +279,7 @@ FK_HD int ukf_quad_step_v4(double (&x)[NX], double (&P)[(NX + LN - 1) / LN][NX],
             FK_UNROLL for (int k = 0; k < NX; ++k) {
                 const double wp = mv.Wp[2 + k];
                 double hl[NZ], wh[NZ];                             // column k of H L, gathered from the lanes that hold its rows
-                FK_UNROLL for (int c = 0; c < NZ; ++c) hl[c] = quad_from<LN>(quad, HLo[c / LN][k], c % LN);
+                FK_UNROLL for (int c = 0; c < NZ; ++c) hl[c] = owner_value<1, LN>(quad, c % LN, HLo[c / LN][k]);
                 FK_UNROLL for (int c = 0; c < NZ; ++c) wh[c] = wp * hl[c];
                 FK_UNROLL for (int r = 0; r < NZ; ++r)
                     FK_UNROLL for (int c = 0; c < NZ; ++c)
@@ -336,7 +320,7 @@ FK_HD int ukf_quad_step_v4(double (&x)[NX], double (&P)[(NX + LN - 1) / LN][NX],
             // x += K (z - zp) ; P -= K (S K') : row b of K from its owner serves x[b] and column b of P
             FK_UNROLL for (int b = 0; b < NX; ++b) {
                 double Kb[NZ], sk[NZ];
-                FK_UNROLL for (int c = 0; c < NZ; ++c) Kb[c] = quad_from<LN>(quad, Ko[(b / LN) * NZ + c], b % LN);
+                FK_UNROLL for (int c = 0; c < NZ; ++c) Kb[c] = owner_value<1, LN>(quad, b % LN, Ko[(b / LN) * NZ + c]);
                 {
                     double acc = Kb[0] * zc[0];
                     FK_UNROLL for (int c = 1; c < NZ; ++c) acc = fma(Kb[c], zc[c], acc);
@@ -400,7 +384,7 @@ FK_HD int ukf_quad_rts_step_v4(double (&x)[NX], double (&P)[(NX + LN - 1) / LN][
             const double wms = mv.Wp[0], wcs = mv.Wp[1];
             double wy[NX];
             FK_UNROLL for (int b = 0; b < NX; ++b) {
-                const double fx = quad_from<LN>(quad, Fxo[b / LN], b % LN);
+                const double fx = owner_value<1, LN>(quad, b % LN, Fxo[b / LN]);
                 xb[b] = wms * fx;
                 wy[b] = wcs * (fx - xb[b]);
             }
@@ -438,7 +422,7 @@ FK_HD int ukf_quad_rts_step_v4(double (&x)[NX], double (&P)[(NX + LN - 1) / LN][
                 const double wp = mv.Wp[2 + k];
                 double wfo[R], wf[NX];
                 FK_UNROLL for (int r = 0; r < R; ++r) wfo[r] = wp * FL[r][k];
-                FK_UNROLL for (int b = 0; b < NX; ++b) wf[b] = quad_from<LN>(quad, wfo[b / LN], b % LN);
+                FK_UNROLL for (int b = 0; b < NX; ++b) wf[b] = owner_value<1, LN>(quad, b % LN, wfo[b / LN]);
                 FK_UNROLL for (int r = 0; r < R; ++r) {
                     if (LN * r + LN - 1 < k) continue;
                     FK_UNROLL for (int b = 0; b < NX; ++b) K[r][b] = (k == 0) ? Lw[r][0] * wf[b] : fma(Lw[r][k], wf[b], K[r][b]);
@@ -457,7 +441,7 @@ FK_HD int ukf_quad_rts_step_v4(double (&x)[NX], double (&P)[(NX + LN - 1) / LN][
                 const double wp = mv.Wp[2 + k];
                 double wfo[R], wf[NX];
                 FK_UNROLL for (int r = 0; r < R; ++r) wfo[r] = wp * FL[r][k];
-                FK_UNROLL for (int b = 0; b < NX; ++b) wf[b] = quad_from<LN>(quad, wfo[b / LN], b % LN);
+                FK_UNROLL for (int b = 0; b < NX; ++b) wf[b] = owner_value<1, LN>(quad, b % LN, wfo[b / LN]);
                 FK_UNROLL for (int r = 0; r < R; ++r)
                     FK_UNROLL for (int b = 0; b < NX; ++b) Pb[r][b] = fma(FL[r][k], wf[b], Pb[r][b]);
                 FK_STAGE();
@@ -497,7 +481,7 @@ FK_HD int ukf_quad_rts_step_v4(double (&x)[NX], double (&P)[(NX + LN - 1) / LN][
         FK_UNROLL for (int i = NX - 1; i >= 0; --i) {
             double col[NX];
             FK_UNROLL for (int k = 0; k < NX; ++k)
-                if (k > i) col[k] = quad_from<LN>(quad, Lb[k / LN][i], k % LN);
+                if (k > i) col[k] = owner_value<1, LN>(quad, k % LN, Lb[k / LN][i]);
             FK_UNROLL for (int r = 0; r < R; ++r) {
                 double acc = K[r][i];
                 FK_UNROLL for (int k = NX - 1; k >= 0; --k)
@@ -518,7 +502,7 @@ FK_HD int ukf_quad_rts_step_v4(double (&x)[NX], double (&P)[(NX + LN - 1) / LN][
             xo[r] = acc;
         }
         io.own_x(x);
-        FK_UNROLL for (int b = 0; b < NX; ++b) x[b] += quad_from<LN>(quad, xo[b / LN], b % LN);
+        FK_UNROLL for (int b = 0; b < NX; ++b) x[b] += owner_value<1, LN>(quad, b % LN, xo[b / LN]);
     }
     FK_STAGE();
     // (eight lanes: the full rows of Ps[k] are requested HERE, a phase ahead of their use -- two row slots per lane leave the room)
@@ -542,7 +526,7 @@ FK_HD int ukf_quad_rts_step_v4(double (&x)[NX], double (&P)[(NX + LN - 1) / LN][
                 const int b = LN * s + q;
                 if (b >= NX) continue;
                 double Db[NX];
-                FK_UNROLL for (int c = 0; c < NX; ++c) Db[c] = quad_from<LN>(quad, Ds[c], q);
+                FK_UNROLL for (int c = 0; c < NX; ++c) Db[c] = owner_value<1, LN>(quad, q, Ds[c]);
                 FK_UNROLL for (int r = 0; r < R; ++r)
                     FK_UNROLL for (int c = 0; c < NX; ++c) T1[r][c] = (b == 0) ? K[r][0] * Db[c] : fma(K[r][b], Db[c], T1[r][c]);
             }
@@ -555,7 +539,7 @@ FK_HD int ukf_quad_rts_step_v4(double (&x)[NX], double (&P)[(NX + LN - 1) / LN][
     }
     FK_UNROLL for (int j = 0; j < NX; ++j) {
         double Kj[NX];
-        FK_UNROLL for (int c = 0; c < NX; ++c) Kj[c] = quad_from<LN>(quad, K[j / LN][c], j % LN);
+        FK_UNROLL for (int c = 0; c < NX; ++c) Kj[c] = owner_value<1, LN>(quad, j % LN, K[j / LN][c]);
         FK_UNROLL for (int r = 0; r < R; ++r) {
             double acc = T1[r][0] * Kj[0];
             FK_UNROLL for (int c = 1; c < NX; ++c) acc = fma(T1[r][c], Kj[c], acc);

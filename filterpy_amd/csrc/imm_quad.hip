@@ -86,47 +86,9 @@ __device__ __forceinline__ void quad_fill(double *dst, const double *__restrict_
     }
 }
 
-// The value lane OWNER of the filter's group holds, in every lane of the group.  Four lanes: one quad-permute DPP move per half.  Eight
-// lanes (a pair of quads, inside a DPP row of 16): every quad broadcasts ITS lane OWNER % 4, then the quad that does not hold the
-// owner takes the other quad's value -- row_shr:4 into the odd quads (bank mask 0xA) or row_shl:4 into the even ones (0x5).
-template <int OWNER>
-__device__ __forceinline__ double grp_bcast(double v)
-{
-    static_assert(OWNER >= 0 && OWNER < LPF, "a lane of the group");
-    if constexpr (LPF == 4) {
-        return quad_bcast<OWNER>(v);
-    } else {
-        constexpr int q = OWNER & 3, h = OWNER >> 2;
-        int lo = __double2loint(v), hi = __double2hiint(v);
-        lo = __builtin_amdgcn_mov_dpp(lo, q * 0x55, 0xf, 0xf, true);
-        hi = __builtin_amdgcn_mov_dpp(hi, q * 0x55, 0xf, 0xf, true);
-        constexpr int ctrl = h == 0 ? 0x114 : 0x104, banks = h == 0 ? 0xA : 0x5;
-        lo = __builtin_amdgcn_update_dpp(lo, lo, ctrl, 0xf, banks, false);
-        hi = __builtin_amdgcn_update_dpp(hi, hi, ctrl, 0xf, banks, false);
-        return __hiloint2double(hi, lo);
-    }
-}
-// The sum of a value over the LPF lanes of the filter's group, in every lane of it: two quad-permute steps, and for eight lanes the
-// other quad's sum over row_shr:4 / row_shl:4 with the bank masks of grp_bcast.
-__device__ __forceinline__ double grp_sum(double v)
-{
-    v += quad_rot<0xB1>(v);      // quad_perm:[1,0,3,2]
-    v += quad_rot<0x4E>(v);      // quad_perm:[2,3,0,1]
-    if constexpr (LPF == 8) {
-        const int lo = __double2loint(v), hi = __double2hiint(v);
-        int plo = __builtin_amdgcn_update_dpp(lo, lo, 0x114, 0xf, 0xA, false);
-        int phi = __builtin_amdgcn_update_dpp(hi, hi, 0x114, 0xf, 0xA, false);
-        plo = __builtin_amdgcn_update_dpp(plo, lo, 0x104, 0xf, 0x5, false);
-        phi = __builtin_amdgcn_update_dpp(phi, hi, 0x104, 0xf, 0x5, false);
-        v += __hiloint2double(phi, plo);
-    }
-    return v;
-}
-// (k: a compile-time constant after unrolling; owner = lane k / R of the group)
-#define FK_Q_OWN_(o, v) grp_bcast<((o) < LPF ? (o) : 0)>(v)
-#define FK_Q_OWNER(k, R, v)                                                                                            \
-    (((k) / (R)) == 0 ? FK_Q_OWN_(0, v) : ((k) / (R)) == 1 ? FK_Q_OWN_(1, v) : ((k) / (R)) == 2 ? FK_Q_OWN_(2, v) : ((k) / (R)) == 3 ? FK_Q_OWN_(3, v) \
-     : ((k) / (R)) == 4 ? FK_Q_OWN_(4, v) : ((k) / (R)) == 5 ? FK_Q_OWN_(5, v) : ((k) / (R)) == 6 ? FK_Q_OWN_(6, v) : FK_Q_OWN_(7, v))
+// the filter's lane group: 4 lanes (a quad) or 8 (a pair of quads) -- broadcasts, the sum over the group (fk_ml.hpp); the owner of row k
+// of a rows-per-lane block is lane k / R of it (fk_owner.hpp; k: a compile-time constant after unrolling)
+using Grp = LaneGroup<LPF>;
 
 // element sub R + r of a replicated vector
 template <int NX>
@@ -163,6 +125,7 @@ template <int NX, class LM>
 __device__ __forceinline__ void quad_predict(double (&x)[NX], double (&P)[NX / LPF][NX], const LM &M0, unsigned sub)
 {
     constexpr int R = NX / LPF;
+    const Grp grp{};
     {
         const LM M = quad_fresh(M0);
         const double *fo = M.s + LM::OFF_F + sub * (unsigned)(R * LM::PX);      // the lane's own rows of F
@@ -172,7 +135,7 @@ __device__ __forceinline__ void quad_predict(double (&x)[NX], double (&P)[NX / L
             FK_UNROLL for (int k = 1; k < NX; ++k) acc = fma(fo[r * LM::PX + k], x[k], acc);
             xo[r] = acc;
         }
-        FK_UNROLL for (int k = 0; k < NX; ++k) x[k] = FK_Q_OWNER(k, R, xo[k % R]);
+        FK_UNROLL for (int k = 0; k < NX; ++k) x[k] = owner_value<R, LPF>(grp, k, xo[k % R]);
     }
     double FP[R][NX];
     {
@@ -185,7 +148,7 @@ __device__ __forceinline__ void quad_predict(double (&x)[NX], double (&P)[NX / L
     FK_UNROLL for (int l = 0; l < NX; ++l) {
         if (l + 1 < NX) { FK_UNROLL for (int r = 0; r < R; ++r) fc[(l + 1) & 1][r] = fo[r * LM::PX + l + 1]; }
         double prow[NX];
-        FK_UNROLL for (int c = 0; c < NX; ++c) prow[c] = FK_Q_OWNER(l, R, P[l % R][c]);
+        FK_UNROLL for (int c = 0; c < NX; ++c) prow[c] = owner_value<R, LPF>(grp, l, P[l % R][c]);
         FK_UNROLL for (int r = 0; r < R; ++r) {
             const double f = fc[l & 1][r];
             FK_UNROLL for (int c = 0; c < NX; ++c) FP[r][c] = (l == 0) ? f * prow[c] : fma(f, prow[c], FP[r][c]);
@@ -218,6 +181,7 @@ __device__ __forceinline__ int quad_update(double (&x)[NX], double (&P)[NX / LPF
                                            double (&y)[NZ], double (&Lf)[NZ * NZ], double (&dinv)[NZ])
 {
     constexpr int R = NX / LPF, ZR = NZ / LPF;
+    const Grp grp{};
     int st = 0;
     double PHT[R][NZ];
     LM M = quad_fresh(M0);
@@ -256,7 +220,7 @@ __device__ __forceinline__ int quad_update(double (&x)[NX], double (&P)[NX / LPF
                     FK_UNROLL for (int c = 0; c < NZ; ++c) rq[q][c] = ro[q * LM::PZ + c];
             }
             double prow[NZ];
-            FK_UNROLL for (int c = 0; c < NZ; ++c) prow[c] = FK_Q_OWNER(k, R, PHT[k % R][c]);
+            FK_UNROLL for (int c = 0; c < NZ; ++c) prow[c] = owner_value<R, LPF>(grp, k, PHT[k % R][c]);
             FK_UNROLL for (int q = 0; q < ZR; ++q) {
                 const double h = hs[(k / 4) & 1][q][k % 4];
                 FK_UNROLL for (int c = 0; c < NZ; ++c) So[q][c] = (k == 0) ? h * prow[c] : fma(h, prow[c], So[q][c]);
@@ -266,7 +230,7 @@ __device__ __forceinline__ int quad_update(double (&x)[NX], double (&P)[NX / LPF
         FK_UNROLL for (int q = 0; q < ZR; ++q)
             FK_UNROLL for (int c = 0; c < NZ; ++c) So[q][c] += rq[q][c];
         FK_UNROLL for (int a = 0; a < NZ; ++a)
-            FK_UNROLL for (int c = 0; c < NZ; ++c) Lf[a * NZ + c] = (c <= a) ? FK_Q_OWNER(a, ZR, So[a % ZR][c]) : 0.0;
+            FK_UNROLL for (int c = 0; c < NZ; ++c) Lf[a * NZ + c] = (c <= a) ? owner_value<ZR, LPF>(grp, a, So[a % ZR][c]) : 0.0;
     }
     FK_STAGE();
     double K[R * NZ];
@@ -285,7 +249,7 @@ __device__ __forceinline__ int quad_update(double (&x)[NX], double (&P)[NX / LPF
             FK_UNROLL for (int k = 0; k < NZ; ++k) acc = fma(K[r * NZ + k], y[k], acc);
             xo[r] = acc;
         }
-        FK_UNROLL for (int k = 0; k < NX; ++k) x[k] = FK_Q_OWNER(k, R, xo[k % R]);
+        FK_UNROLL for (int k = 0; k < NX; ++k) x[k] = owner_value<R, LPF>(grp, k, xo[k % R]);
     }
     // Joseph form.  T1 = (I - K H) P = P - K (H P), column by column in place, WITHOUT assuming P symmetric: P is held by rows and
     // its two triangles round differently; with (P H')' in the place of H P that rounding asymmetry is amplified instead of
@@ -302,7 +266,7 @@ __device__ __forceinline__ int quad_update(double (&x)[NX], double (&P)[NX / LPF
             FK_UNROLL for (int c = 0; c < NZ; ++c) {
                 double acc = hown[c][0] * P[0][j];
                 FK_UNROLL for (int r = 1; r < R; ++r) acc = fma(hown[c][r], P[r][j], acc);
-                hp[c] = grp_sum(acc);
+                hp[c] = grp.sum(acc);
             }
             FK_UNROLL for (int r = 0; r < R; ++r) {
                 double acc = P[r][j];
@@ -335,7 +299,7 @@ __device__ __forceinline__ int quad_update(double (&x)[NX], double (&P)[NX / LPF
     // P+ = T1 + D K'
     FK_UNROLL for (int j = 0; j < NX; ++j) {
         double krow[NZ];
-        FK_UNROLL for (int c = 0; c < NZ; ++c) krow[c] = FK_Q_OWNER(j, R, K[(j % R) * NZ + c]);
+        FK_UNROLL for (int c = 0; c < NZ; ++c) krow[c] = owner_value<R, LPF>(grp, j, K[(j % R) * NZ + c]);
         FK_UNROLL for (int r = 0; r < R; ++r) {
             double acc = P[r][j];
             FK_UNROLL for (int c = 0; c < NZ; ++c) acc = fma(D[r][c], krow[c], acc);

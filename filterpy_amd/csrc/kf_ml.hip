@@ -186,6 +186,7 @@ kf_ml_kernel(const KfArgs a_in)
     constexpr int HAUX = PERS ? 16 : 0;      // cache policy of the state hand-over: sc1 = agent scope (MlView::load / store)
     KfArgs a = a_in;
     constexpr int NX = 3 * R;
+    const LaneGroup<3> tri{};
     using LM = LdsModel<NX, NZ>;
     constexpr bool AOS = LAYOUT == LAYOUT_AOS;
     constexpr int TILE = 16 * NX + 16 * NX * NX;                 // AOS: one (x, P) output set of a wave
@@ -460,24 +461,18 @@ kf_ml_kernel(const KfArgs a_in)
                 FK_UNROLL for (int k = 0; k < NX; ++k) {
                     if (k + 1 < NX) hk[(k + 1) & 1][0] = hrow[k + 1];
                     double pk[NZ];
-                    FK_UNROLL for (int c = 0; c < NZ; ++c) {
-                        const double v = PHT[k % R][c];
-                        pk[c] = (k / R == 0) ? quad_bcast<0>(v) : (k / R == 1) ? quad_bcast<1>(v) : quad_bcast<2>(v);
-                    }
+                    FK_OWNER_ROW(R, tri, pk, PHT, k);
                     const double h = hk[k & 1][0];
                     FK_UNROLL for (int c = 0; c < NZ; ++c) Srow[c] = (k == 0) ? h * pk[c] : fma(h, pk[c], Srow[c]);
                     if (k % 3 == 2) FK_STAGE();
                 }
                 FK_UNROLL for (int r = 0; r < NZ; ++r)
                     FK_UNROLL for (int c = 0; c < NZ; ++c)
-                        S[r * NZ + c] = (r == 0) ? quad_bcast<0>(Srow[c]) : (r == 1) ? quad_bcast<1>(Srow[c]) : quad_bcast<2>(Srow[c]);
+                        S[r * NZ + c] = owner_value<1, 3>(tri, r, Srow[c]);      // (one row per lane)
             }
             FK_UNROLL for (int k = 0; k < NX && !HLDS; ++k) {
                 double pk[NZ];
-                FK_UNROLL for (int c = 0; c < NZ; ++c) {
-                    const double v = PHT[k % R][c];
-                    pk[c] = (k / R == 0) ? quad_bcast<0>(v) : (k / R == 1) ? quad_bcast<1>(v) : quad_bcast<2>(v);
-                }
+                FK_OWNER_ROW(R, tri, pk, PHT, k);
                 FK_UNROLL for (int r = 0; r < NZ; ++r) {
                     const double h = HX(r * NX + k);
                     FK_UNROLL for (int c = 0; c < NZ; ++c)
@@ -511,7 +506,7 @@ kf_ml_kernel(const KfArgs a_in)
                     FK_UNROLL for (int r = 1; r < R; ++r) acc = fma(hc[c & 1][r], P[r][j], acc);
                     HP[c][j] = acc;
                 }
-                FK_UNROLL for (int j = 0; j < NX; ++j) HP[c][j] = (HP[c][j] + quad_rot<0x09>(HP[c][j])) + quad_rot<0x52>(HP[c][j]);
+                FK_UNROLL for (int j = 0; j < NX; ++j) HP[c][j] = tri.sum(HP[c][j]);
                 FK_STAGE();
             }
             // T1 = P - K (H P) (own rows, in place)
@@ -560,10 +555,7 @@ kf_ml_kernel(const KfArgs a_in)
             // P+ = T1 + D K' : column j needs K's row j from its owner; the same row updates x[j]
             FK_UNROLL for (int j = 0; j < NX; ++j) {
                 double Kj[NZ];
-                FK_UNROLL for (int c = 0; c < NZ; ++c) {
-                    const double v = K[j % R][c];
-                    Kj[c] = (j / R == 0) ? quad_bcast<0>(v) : (j / R == 1) ? quad_bcast<1>(v) : quad_bcast<2>(v);
-                }
+                FK_OWNER_ROW(R, tri, Kj, K, j);
                 double xa = x[j];
                 FK_UNROLL for (int c = 0; c < NZ; ++c) xa = fma(Kj[c], y[c], xa);
                 x[j] = xa;
@@ -628,8 +620,7 @@ kf_ml_kernel(const KfArgs a_in)
                 FK_UNROLL for (int c = 0; c < NX; ++c) vP.store(r * NX + c, P[r][c]);
         }
         if (a.status) {
-            int s = st | (fin ? 0 : ST_NONFINITE);
-            s |= __builtin_amdgcn_mov_dpp(s, 0x55 * 1, 0xf, 0xf, true) | __builtin_amdgcn_mov_dpp(s, 0x55 * 2, 0xf, 0xf, true);
+            const int s = tri.any_lane0(st | (fin ? 0 : ST_NONFINITE));
             if (L == 0) {
                 if constexpr (PERS) status_merge_agent(a.status, trk, a.status_or, s);
                 else a.status[trk] = a.status_or ? (a.status[trk] | s) : s;
@@ -667,13 +658,6 @@ __device__ __forceinline__ void ml_store_rows_aos_park(const double (&M)[R][NX],
     ml_wave_fence();
 }
 
-// row k of a rows-per-lane matrix, delivered to every lane of the quad by its owner
-#define FK_ROW_FROM_OWNER(dst, M, k, LEN)                                                                     \
-    FK_UNROLL for (int j_ = 0; j_ < (LEN); ++j_) {                                                            \
-        const double v_ = M[(k) % R][j_];                                                                     \
-        dst[j_] = ((k) / R == 0) ? quad_bcast<0>(v_) : ((k) / R == 1) ? quad_bcast<1>(v_) : quad_bcast<2>(v_); \
-    }
-
 // rts_smoother for dim_x = 9 on the same three-lanes-per-track layout (kalman_filter.py:1066-1072):
 //   Pp = F P F' + Q ;  K = (P F') Pp^-1 ;  x += K (xn - F x) ;  P += K (Pn - Pp) K'
 // T = P F' and every row of Pp, K, E = K (Pn - Pp) and P live in the lane that owns the row; rows of
@@ -689,6 +673,7 @@ rts_ml_kernel(const RtsArgs a_in)
 {
     constexpr int HAUX = PERS ? 16 : 0;      // sc1 = agent scope (MlView::load / store)
     constexpr int NX = 3 * R, PL = NX * (NX + 1) / 2;
+    const LaneGroup<3> tri{};
     __shared__ double smem[2 * NX * NX];
     // x and xn - F x are parked here ([element][lane]: conflict-free) across the E = K D stage: spilled
     // to scratch instead, their reloads would be vector-memory operations that retire in order behind
@@ -821,7 +806,7 @@ rts_ml_kernel(const RtsArgs a_in)
                 FK_UNROLL for (int r = 0; r < R; ++r) fq[(q + 1) & 1][r] = myF[r * NX + q + 1];
             }
             double Tq[NX];
-            FK_ROW_FROM_OWNER(Tq, Tm, q, NX);
+            FK_OWNER_ROW(R, tri, Tq, Tm, q);
             FK_UNROLL for (int r = 0; r < R; ++r) {
                 const double f = fq[q & 1][r];
                 FK_UNROLL for (int j = 0; j < NX; ++j) Pp[r][j] = (q == 0) ? f * Tq[j] : fma(f, Tq[j], Pp[r][j]);
@@ -851,7 +836,7 @@ rts_ml_kernel(const RtsArgs a_in)
             FK_UNROLL for (int i = 0; i < NX; ++i)
                 FK_UNROLL for (int j = i; j < NX; ++j) {
                     const double v = Pp[i % R][j];
-                    Pf[sym_idx<NX>(i, j)] = (i / R == 0) ? quad_bcast<0>(v) : (i / R == 1) ? quad_bcast<1>(v) : quad_bcast<2>(v);
+                    Pf[sym_idx<NX>(i, j)] = owner_value<R, 3>(tri, i, v);
                 }
             FK_STAGE();
             if (!ldlt_packed<NX>(Pf, d, dinv)) st |= ST_NOT_PD;
@@ -891,7 +876,7 @@ rts_ml_kernel(const RtsArgs a_in)
                 FK_STAGE();
                 FK_UNROLL for (int i = 0; i < NX; ++i) {
                     const double v = fxo[i % R];
-                    const double fx = (i / R == 0) ? quad_bcast<0>(v) : (i / R == 1) ? quad_bcast<1>(v) : quad_bcast<2>(v);
+                    const double fx = owner_value<R, 3>(tri, i, v);
                     dx[i] = xn[i] - fx;
                 }
                 FK_STAGE();
@@ -905,7 +890,7 @@ rts_ml_kernel(const RtsArgs a_in)
             double E[R][NX];
             FK_UNROLL for (int q = 0; q < NX; ++q) {
                 double Dq[NX];
-                FK_ROW_FROM_OWNER(Dq, Pn, q, NX);
+                FK_OWNER_ROW(R, tri, Dq, Pn, q);
                 FK_UNROLL for (int r = 0; r < R; ++r) {
                     const double kq = Tm[r][q];
                     FK_UNROLL for (int j = 0; j < NX; ++j) E[r][j] = (q == 0) ? kq * Dq[j] : fma(kq, Dq[j], E[r][j]);
@@ -927,10 +912,10 @@ rts_ml_kernel(const RtsArgs a_in)
             FK_STAGE();
             FK_UNROLL for (int j = 0; j < NX; ++j) {
                 double Kj[NX];
-                FK_ROW_FROM_OWNER(Kj, Tm, j, NX);
+                FK_OWNER_ROW(R, tri, Kj, Tm, j);
                 {
                     const double v = xao[j % R];
-                    xn[j] = (j / R == 0) ? quad_bcast<0>(v) : (j / R == 1) ? quad_bcast<1>(v) : quad_bcast<2>(v);
+                    xn[j] = owner_value<R, 3>(tri, j, v);
                 }
                 FK_UNROLL for (int r = 0; r < R; ++r) {
                     double acc = Pn[r][j];
@@ -959,8 +944,7 @@ rts_ml_kernel(const RtsArgs a_in)
         bool fin = all_finite<NX>(xn);
         FK_UNROLL for (int r = 0; r < R; ++r)
             FK_UNROLL for (int c = 0; c < NX; ++c) fin = fin && (fabs(Pn[r][c]) <= 1.79769313486231570815e+308);
-        int s = st | (fin ? 0 : ST_NONFINITE);
-        s |= __builtin_amdgcn_mov_dpp(s, 0x55 * 1, 0xf, 0xf, true) | __builtin_amdgcn_mov_dpp(s, 0x55 * 2, 0xf, 0xf, true);
+        const int s = tri.any_lane0(st | (fin ? 0 : ST_NONFINITE));
         if (L == 0) {
             if constexpr (PERS) status_merge_agent(a.status, trk, a.status_or, s);
             else a.status[trk] = a.status_or ? (a.status[trk] | s) : s;

@@ -60,10 +60,7 @@
                         FK_UNROLL for (int j = 0; j < NX; ++j) Qr[r][j] = myQ[r * NX + j];
                 }
                 double Tk[NX];
-                FK_UNROLL for (int j = 0; j < NX; ++j) {
-                    const double v = T[k % R][j];
-                    Tk[j] = (k / R == 0) ? quad_bcast<0>(v) : (k / R == 1) ? quad_bcast<1>(v) : quad_bcast<2>(v);
-                }
+                FK_OWNER_ROW(R, tri, Tk, T, k);
                 if (k == NX - 1) {
                     FK_UNROLL for (int j = 0; j < NX; ++j) Qr[R - 1][j] = myQ[(R - 1) * NX + j];
                 }
@@ -76,7 +73,7 @@
             }
             FK_UNROLL for (int i = 0; i < NX; ++i) {
                 const double v = xo[i % R];
-                x[i] = (i / R == 0) ? quad_bcast<0>(v) : (i / R == 1) ? quad_bcast<1>(v) : quad_bcast<2>(v);
+                x[i] = owner_value<R, 3>(tri, i, v);
             }
             if constexpr (VAR) {
                 // x = (F x) + (B u): the product first, like dot(F, x) + dot(B, u)  (kalman_filter.py:472-475);

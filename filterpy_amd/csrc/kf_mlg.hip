@@ -45,32 +45,12 @@
 namespace fk {
 namespace FK_MLG_CAT(mlg_, FK_NX, FK_NZ) {
 
-// value v of row K's owner (lane K / R of the quad); K is a compile-time constant wherever this is used
-template <int OWNER>
-__device__ __forceinline__ double from_owner(double v)
-{
-    static_assert(OWNER >= 0 && OWNER < 4, "four lanes per track");
-    return quad_bcast<OWNER>(v);
-}
-#define FK_OWNER_ROW(dst, M, k, LEN)                                              \
-    FK_UNROLL for (int j_ = 0; j_ < (LEN); ++j_) {                                \
-        const double v_ = M[(k) % R][j_];                                         \
-        dst[j_] = ((k) / R == 0) ? from_owner<0>(v_) : ((k) / R == 1) ? from_owner<1>(v_) \
-                : ((k) / R == 2) ? from_owner<2>(v_) : from_owner<3>(v_);         \
-    }
-
-// sum over the four lanes of a quad, the same bits in every lane: (a0 + a1) + (a2 + a3) in lanes 0, 1 and
-// (a2 + a3) + (a0 + a1) in lanes 2, 3 (fp addition commutes)
-__device__ __forceinline__ double quad_sum(double v)
-{
-    v += quad_rot<0xB1>(v);      // quad_perm:[1,0,3,2]
-    v += quad_rot<0x4E>(v);      // quad_perm:[2,3,0,1]
-    return v;
-}
-
 // AOS ([track][element], NumPy order) output of one (x, P) set: a wave's 16 tracks are one contiguous slab; the quads
 // write their rows into a wave-private LDS tile laid out like the slab, then the 64 lanes copy consecutive 16-byte
 // units (1 KiB per store instruction).  The descriptor is sized to the wave's valid tracks: the range check drops the tail.
+// (x and P share ONE pair of fences and both descriptors are formed in front of the first copy-out: as an x half followed by
+// ml_store_rows_aos, or as two ml_tile_out_aos calls, the NumPy-order kernels of this file come out with another schedule:
+// docs/MEASUREMENTS.md, "The lane-group exchanges stated once".)
 template <int R, int NX>
 __device__ __forceinline__ void mlg_store_aos(const double (&x)[NX], const double (&P)[R][NX], const unsigned (&row)[R],
                                               double *xdst, double *Pdst, double *tile, unsigned lane, unsigned valid)
@@ -111,6 +91,7 @@ __global__ void __launch_bounds__(BLOCK, (EX ? 1 : NX <= 8 ? 3 : NX <= 9 ? 2 : 1
 kf_mlg_kernel(const KfArgs a)
 {
     constexpr int R = (NX + 3) / 4;
+    const LaneGroup<4> quad{};
     using LM = LdsModel<NX, NZ>;
     constexpr bool AOS = LAYOUT == LAYOUT_AOS;
     constexpr int TILE = 16 * NX + 16 * NX * NX;                 // AOS: one (x, P) output set of a wave
@@ -351,7 +332,7 @@ kf_mlg_kernel(const KfArgs a)
                         FK_UNROLL for (int r = 0; r < NZ; ++r) hk[(k + 1) & 1][r] = sH[r * NX + k + 1];
                     }
                     double pk[NZ];
-                    FK_OWNER_ROW(pk, PHT, k, NZ);
+                    FK_OWNER_ROW(R, quad, pk, PHT, k);
                     FK_UNROLL for (int r = 0; r < NZ; ++r)
                         FK_UNROLL for (int c = 0; c < NZ; ++c)
                             S[r * NZ + c] = (k == 0) ? hk[k & 1][r] * pk[c] : fma(hk[k & 1][r], pk[c], S[r * NZ + c]);
@@ -420,7 +401,7 @@ kf_mlg_kernel(const KfArgs a)
                 FK_UNROLL for (int j = 0; j < NX; ++j) {
                     double acc = hc[0] * P[0][j];
                     FK_UNROLL for (int r = 1; r < R; ++r) acc = fma(hc[r], P[r][j], acc);
-                    HP[c][j] = quad_sum(acc);
+                    HP[c][j] = quad.sum(acc);
                 }
                 FK_STAGE();
             }
@@ -458,7 +439,7 @@ kf_mlg_kernel(const KfArgs a)
             // P+ = T1 + D K' : column j needs K's row j from its owner; the same row updates x[j]
             FK_UNROLL for (int j = 0; j < NX; ++j) {
                 double Kj[NZ];
-                FK_OWNER_ROW(Kj, K, j, NZ);
+                FK_OWNER_ROW(R, quad, Kj, K, j);
                 double xa = x[j];
                 FK_UNROLL for (int c = 0; c < NZ; ++c) xa = fma(Kj[c], y[c], xa);
                 x[j] = xa;
@@ -540,9 +521,7 @@ kf_mlg_kernel(const KfArgs a)
             }
         }
         if (a.status) {
-            int s = st | (fin ? 0 : ST_NONFINITE);
-            s |= __builtin_amdgcn_mov_dpp(s, 0xB1, 0xf, 0xf, true);
-            s |= __builtin_amdgcn_mov_dpp(s, 0x4E, 0xf, 0xf, true);
+            const int s = quad.any(st | (fin ? 0 : ST_NONFINITE));
             if (L == 0) a.status[trk] = a.status_or ? (a.status[trk] | s) : s;
         }
     }

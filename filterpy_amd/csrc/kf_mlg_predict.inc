@@ -50,7 +50,7 @@
                     FK_UNROLL for (int r = 0; r < R; ++r) fk[(k + 1) & 1][r] = sF[row[r] * NX + k + 1];
                 }
                 double Tk[NX];
-                FK_OWNER_ROW(Tk, T, k, NX);
+                FK_OWNER_ROW(R, quad, Tk, T, k);
                 if (k == NX - 1) {             // (T's rows are spent once their last broadcast is out)
                     FK_UNROLL for (int r = 0; r < R; ++r)
                         FK_UNROLL for (int j = 0; j < NX; ++j) Qr[r][j] = sQ[row[r] * NX + j];

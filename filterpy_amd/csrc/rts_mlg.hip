@@ -35,38 +35,12 @@
 namespace fk {
 namespace FK_RMLG_CAT(rmlg_, FK_NX) {
 
-#define FK_OWNER_VAL(v_, k) (((k) / R == 0) ? quad_bcast<0>(v_) : ((k) / R == 1) ? quad_bcast<1>(v_) \
-                             : ((k) / R == 2) ? quad_bcast<2>(v_) : quad_bcast<3>(v_))
-#define FK_OWNER_ROW(dst, M, k, LEN)                          \
-    FK_UNROLL for (int j_ = 0; j_ < (LEN); ++j_) {            \
-        const double v_ = M[(k) % R][j_];                     \
-        dst[j_] = FK_OWNER_VAL(v_, k);                        \
-    }
-
-// AOS output of one row-block matrix (the wave's 16 x NX*NX slab) through the wave's LDS tile
-template <int R, int NX>
-__device__ __forceinline__ void store_rows_aos(const double (&M)[R][NX], const unsigned (&row)[R], double *dst, double *tile,
-                                               unsigned lane, unsigned valid)
-{
-    constexpr int EP = NX * NX, UP = 16 * EP / 2;
-    using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-    const unsigned q = lane >> 2;
-    ml_wave_fence();
-    FK_UNROLL for (int r = 0; r < R; ++r)
-        FK_UNROLL for (int c = 0; c < NX; ++c) tile[q * EP + row[r] * NX + c] = M[r][c];
-    ml_wave_fence();
-    const rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc(dst, 0, (int)(valid * (unsigned)EP * 8u), 0x00020000);
-    ml_copy_units<UP, 4>(lane, [&](unsigned unit) { return tile + 2u * unit; },
-                         [&](unsigned unit, bool ok, const u32x4 &v) {
-                             __builtin_amdgcn_raw_buffer_store_b128(v, rP, ok ? unit * 16u : ML_OFF_DROP, 0, 0);
-                         });
-}
-
 template <int NX, int LAYOUT>
 __global__ void __launch_bounds__(BLOCK, (NX <= 8 ? FK_RMLG8_WAVES : NX <= 9 ? 2 : 1))
 rts_mlg_kernel(const RtsArgs a)
 {
     constexpr int R = (NX + 3) / 4;
+    const LaneGroup<4> quad{};
     constexpr bool AOS = LAYOUT == LAYOUT_AOS;
     constexpr bool SOA_SLAB = !AOS && NX <= FK_SOA_SLAB_MAX;      // SOA row blocks through the slab too (16-byte units): n = 10: 0.36 -> 0.45 of HBM, n = 14: 0.32 -> 0.30
     // One wave-private LDS region, used in turn as the AOS staging slab (16 x NX*NX doubles) and as the PARK of a
@@ -119,7 +93,7 @@ rts_mlg_kernel(const RtsArgs a)
     }
 #define FK_STORE_ROWS(base, step, M)                                                   \
     if constexpr (AOS) {                                                               \
-        store_rows_aos<R, NX>(M, row, (base) + ((step) * N + w0) * NX * NX, tile, lane, valid); \
+        ml_store_rows_aos<R, NX, 16>(M, row, (base) + ((step) * N + w0) * NX * NX, tile, lane, valid); \
     } else if constexpr (SOA_SLAB) {                                                   \
         ml_store_rows_soa_slab<R, NX, 16>(M, row, (base) + (step) * ps_blk, N, w0, tile, lane, lane >> 2, valid); \
     } else {                                                                           \
@@ -204,7 +178,7 @@ rts_mlg_kernel(const RtsArgs a)
                     FK_UNROLL for (int r = 0; r < R; ++r) fq[(q + 1) & 1][r] = sF[row[r] * NX + q + 1];
                 }
                 double Tq[NX];
-                FK_OWNER_ROW(Tq, Tm, q, NX);
+                FK_OWNER_ROW(R, quad, Tq, Tm, q);
                 FK_UNROLL for (int r = 0; r < R; ++r) {
                     const double f = fq[q & 1][r];
                     FK_UNROLL for (int j = 0; j < NX; ++j) Pp[r][j] = (q == 0) ? f * Tq[j] : fma(f, Tq[j], Pp[r][j]);
@@ -247,9 +221,9 @@ rts_mlg_kernel(const RtsArgs a)
             FK_UNROLL for (int j = 0; j < NX; ++j) {
                 double Lj[NX];
                 FK_UNROLL for (int q = 0; q < NX; ++q)
-                    if (q < j) { const double v = Pp[j % R][q]; Lj[q] = FK_OWNER_VAL(v, j); }
+                    if (q < j) { const double v = Pp[j % R][q]; Lj[q] = owner_value<R, 4>(quad, j, v); }
                 const double ajj = Pp[j % R][j];
-                double dj = FK_OWNER_VAL(ajj, j);
+                double dj = owner_value<R, 4>(quad, j, ajj);
                 FK_UNROLL for (int q = 0; q < NX; ++q)
                     if (q < j) dj = fma(-Lj[q] * Lj[q], d[q], dj);
                 pd = pd && (dj > 0.0);
@@ -271,7 +245,7 @@ rts_mlg_kernel(const RtsArgs a)
             FK_UNROLL for (int i = 1; i < NX; ++i) {
                 double Li[NX];
                 FK_UNROLL for (int q = 0; q < NX; ++q)
-                    if (q < i) { const double v = Pp[i % R][q]; Li[q] = FK_OWNER_VAL(v, i); }
+                    if (q < i) { const double v = Pp[i % R][q]; Li[q] = owner_value<R, 4>(quad, i, v); }
                 FK_UNROLL for (int r = 0; r < R; ++r) {
                     double t = Tm[r][i];
                     FK_UNROLL for (int q = 0; q < NX; ++q)
@@ -288,7 +262,9 @@ rts_mlg_kernel(const RtsArgs a)
                 FK_UNROLL for (int q = 0; q < NX; ++q)
                     if (q > i) {
                         const double v = Pp[q % R][i];
-                        const double lqi = FK_OWNER_VAL(v, q);
+                        // (the ladder in place, once: through owner_value the dim_x 15 and 16 instantiations come out with
+                        //  another schedule and other spills -- docs/MEASUREMENTS.md)
+                        const double lqi = (q / R == 0) ? quad.bcast<0>(v) : (q / R == 1) ? quad.bcast<1>(v) : (q / R == 2) ? quad.bcast<2>(v) : quad.bcast<3>(v);
                         FK_UNROLL for (int r = 0; r < R; ++r) t[r] = fma(-lqi, Tm[r][q], t[r]);
                     }
                 FK_UNROLL for (int r = 0; r < R; ++r) Tm[r][i] = t[r];
@@ -304,7 +280,7 @@ rts_mlg_kernel(const RtsArgs a)
                 FK_UNROLL for (int j = 0; j < NX; ++j) D[r][j] = park[(r * NX + j) * 64];
             FK_UNROLL for (int q = 0; q < NX; ++q) {
                 double Dq[NX];
-                FK_OWNER_ROW(Dq, D, q, NX);
+                FK_OWNER_ROW(R, quad, Dq, D, q);
                 FK_UNROLL for (int r = 0; r < R; ++r) {
                     const double kq = Tm[r][q];
                     FK_UNROLL for (int j = 0; j < NX; ++j) E[r][j] = (q == 0) ? kq * Dq[j] : fma(kq, Dq[j], E[r][j]);
@@ -342,7 +318,7 @@ rts_mlg_kernel(const RtsArgs a)
             double xn[NX];
             FK_UNROLL for (int j = 0; j < NX; ++j) {
                 double Kj[NX];
-                FK_OWNER_ROW(Kj, Tm, j, NX);
+                FK_OWNER_ROW(R, quad, Kj, Tm, j);
                 double xa = x[j];
                 FK_UNROLL for (int q = 0; q < NX; ++q) xa = fma(Kj[q], dx[q], xa);
                 xn[j] = xa;
@@ -373,9 +349,7 @@ rts_mlg_kernel(const RtsArgs a)
         bool fin = all_finite<NX>(xn);
         FK_UNROLL for (int r = 0; r < R; ++r)
             FK_UNROLL for (int c = 0; c < NX; ++c) fin = fin && (fabs(park[(r * NX + c) * 64]) <= 1.79769313486231570815e+308);
-        int s = st | (fin ? 0 : ST_NONFINITE);
-        s |= __builtin_amdgcn_mov_dpp(s, 0xB1, 0xf, 0xf, true);
-        s |= __builtin_amdgcn_mov_dpp(s, 0x4E, 0xf, 0xf, true);
+        const int s = quad.any(st | (fin ? 0 : ST_NONFINITE));
         if (L == 0) a.status[trk] = a.status_or ? (a.status[trk] | s) : s;
     }
 #undef FK_ROWS_HERE

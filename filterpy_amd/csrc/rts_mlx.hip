@@ -37,26 +37,6 @@ namespace FK_RMLX_CAT(rmlx_, FK_NX) {
 constexpr int LPT = 8;                        // lanes per track
 constexpr int TPW = 64 / LPT;                 // tracks per wave
 
-// AOS output of one row-block matrix (the wave's TPW x NX*NX slab) through an idle park
-template <int R, int NX>
-__device__ __forceinline__ void store_rows_aos(const double (&M)[R][NX], const unsigned (&row)[R], double *dst, double *tile,
-                                               unsigned lane, unsigned valid)
-{
-    constexpr int EP = NX * NX, UP = TPW * EP / 2;
-    using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-    const unsigned g = lane / LPT;
-    ml_wave_fence();
-    FK_UNROLL for (int r = 0; r < R; ++r)
-        FK_UNROLL for (int c = 0; c < NX; ++c) tile[g * EP + row[r] * NX + c] = M[r][c];
-    ml_wave_fence();
-    const rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc(dst, 0, (int)(valid * (unsigned)EP * 8u), 0x00020000);
-    ml_copy_units<UP, 4>(lane, [&](unsigned unit) { return tile + 2u * unit; },
-                         [&](unsigned unit, bool ok, const u32x4 &v) {
-                             __builtin_amdgcn_raw_buffer_store_b128(v, rP, ok ? unit * 16u : ML_OFF_DROP, 0, 0);
-                         });
-    ml_wave_fence();
-}
-
 template <int NX, int LAYOUT>
 __global__ void __launch_bounds__(BLOCK, 1)
 rts_mlx_kernel(const RtsArgs a)
@@ -103,7 +83,8 @@ rts_mlx_kernel(const RtsArgs a)
     }
 #define FK_STORE_ROWS(base, step, M, tile)                                             \
     if constexpr (AOS) {                                                               \
-        store_rows_aos<R, NX>(M, row, (base) + ((step) * N + w0) * NX * NX, tile, lane, valid); \
+        ml_store_rows_aos<R, NX, TPW>(M, row, (base) + ((step) * N + w0) * NX * NX, tile, lane, valid); \
+        ml_wave_fence();                              /* the tile is a park: the next use writes it */ \
     } else {                                                                           \
         ml_store_rows_soa_slab<R, NX, TPW>(M, row, (base) + (step) * ps_blk, N, w0, tile, lane, lane / LPT, valid); \
     }
@@ -278,11 +259,7 @@ rts_mlx_kernel(const RtsArgs a)
         bool fin = all_finite<NX>(xn);
         FK_UNROLL for (int r = 0; r < R; ++r)
             FK_UNROLL for (int c = 0; c < NX; ++c) fin = fin && (fabs(mineB[(r * NX + c) * 64]) <= 1.79769313486231570815e+308);
-        int s = st | (fin ? 0 : ST_NONFINITE);
-        // OR over the eight lanes of the group (two quads): within the quad by DPP, across by a row shift
-        s |= __builtin_amdgcn_mov_dpp(s, 0xB1, 0xf, 0xf, true);
-        s |= __builtin_amdgcn_mov_dpp(s, 0x4E, 0xf, 0xf, true);
-        s |= __builtin_amdgcn_mov_dpp(s, 0x104, 0xf, 0xf, true);      // row_shl:4 : lanes 0..3 of the group see lanes 4..7
+        const int s = LaneGroup<LPT>::any_lane0(st | (fin ? 0 : ST_NONFINITE));
         if (L == 0) a.status[trk] = s;
     }
 #undef FK_FROM

@@ -297,3 +297,63 @@ extern "C" int hc_ukf_oct_v4(int n, int m, long T, const double *F, const double
 #undef GO
     return -1;
 }
+
+// ---- the owner ladder of the several-lane kernels (filterpy_amd/csrc/fk_owner.hpp) over a RECORDING exchange object: bcast<O> notes
+// O and hands the value back
+namespace {
+
+template <int LPT>
+struct RecordingGroup {
+    static constexpr int LANES = LPT;
+    int count = 0, first = -1, mixed = 0;
+    template <int O>
+    double bcast(double v)
+    {
+        if (count == 0) first = O;
+        else if (O != first) mixed = 1;
+        ++count;
+        return v;
+    }
+};
+
+template <int R, int LPT>
+int owner_value_probe(int k, double v, int *n_bcast, double *out)
+{
+    RecordingGroup<LPT> rec;
+    *out = fk::owner_value<R, LPT>(rec, k, v);
+    *n_bcast = rec.count;
+    return rec.first;
+}
+
+}  // namespace
+
+// the lane owner_value<R, LPT> takes row k's value from; *n_bcast: how many broadcasts it issued; *out: what it returned
+extern "C" int hc_owner_value(int lpt, int R, int k, double v, int *n_bcast, double *out)
+{
+#define GO(RV, LV) if (R == RV && lpt == LV) return owner_value_probe<RV, LV>(k, v, n_bcast, out)
+#define GOR(RV) GO(RV, 3); GO(RV, 4); GO(RV, 8)
+    GOR(1); GOR(2); GOR(3); GOR(4); GOR(5); GOR(6);
+#undef GOR
+#undef GO
+    return -1;
+}
+
+// FK_OWNER_ROW on four lanes with R = 3 rows per lane, NX = 10 (lane 3 holds row 9 and two clamped duplicates of it): for every row
+// k the lane all NX broadcasts came from (-1: not one lane), their number, and which slot of M they read (M[r][j] = 100 r + j)
+extern "C" void hc_owner_row_4_3_10(int *lane, int *n_bcast, int *slot)
+{
+    constexpr int R = 3, NX = 10;
+    double M[R][NX];
+    for (int r = 0; r < R; ++r)
+        for (int j = 0; j < NX; ++j) M[r][j] = 100.0 * r + j;
+    for (int k = 0; k < NX; ++k) {
+        RecordingGroup<4> rec;
+        double dst[NX];
+        FK_OWNER_ROW(R, rec, dst, M, k);
+        lane[k] = rec.mixed ? -1 : rec.first;
+        n_bcast[k] = rec.count;
+        slot[k] = (int)(dst[0] / 100.0);
+        for (int j = 0; j < NX; ++j)
+            if (dst[j] != 100.0 * slot[k] + j) slot[k] = -1;
+    }
+}

@@ -17,7 +17,7 @@ HC = os.path.join(ROOT, "tests", "hostcheck")
 
 def _host_lib():
     so, src = os.path.join(HC, "libhostcheck_quad.so"), os.path.join(HC, "hostcheck_quad.cpp")
-    deps = [src] + [os.path.join(ROOT, "filterpy_amd", "csrc", h) for h in ("fk_ukf_quad.hpp", "fk_ukf.hpp", "fk_math.hpp", "fk_math_sym.hpp")]
+    deps = [src] + [os.path.join(ROOT, "filterpy_amd", "csrc", h) for h in ("fk_ukf_quad.hpp", "fk_owner.hpp", "fk_ukf.hpp", "fk_math.hpp", "fk_math_sym.hpp")]
     _build(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=on", "-w", "-o", so, src], so, deps)
     return ctypes.CDLL(so)
 

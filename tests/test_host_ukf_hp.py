@@ -36,7 +36,7 @@ def _lib(name, src, headers, emulate):
 
 
 ONE_H = ("fk_math.hpp", "fk_math_sym.hpp", "fk_imm.hpp", "fk_exact_scan.hpp", "fk_ukf.hpp")
-QUAD_H = ("fk_ukf_quad.hpp", "fk_ukf.hpp", "fk_math.hpp", "fk_math_sym.hpp")
+QUAD_H = ("fk_ukf_quad.hpp", "fk_owner.hpp", "fk_ukf.hpp", "fk_math.hpp", "fk_math_sym.hpp")
 
 
 @pytest.fixture(scope="module")

@@ -20,7 +20,7 @@ HC = os.path.join(ROOT, "tests", "hostcheck")
 @pytest.fixture(scope="module")
 def quad_lib():
     so, src = os.path.join(HC, "libhostcheck_quad.so"), os.path.join(HC, "hostcheck_quad.cpp")
-    deps = [src] + [os.path.join(ROOT, "filterpy_amd", "csrc", h) for h in ("fk_ukf_quad.hpp", "fk_ukf.hpp", "fk_math.hpp", "fk_math_sym.hpp")]
+    deps = [src] + [os.path.join(ROOT, "filterpy_amd", "csrc", h) for h in ("fk_ukf_quad.hpp", "fk_owner.hpp", "fk_ukf.hpp", "fk_math.hpp", "fk_math_sym.hpp")]
     _build(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=on", "-w", "-o", so, src], so, deps)
     return ctypes.CDLL(so)
 
@@ -255,3 +255,26 @@ def test_oct_filter_step_matches_the_oracle_and_the_quad(quad_lib, n, m):
     assert rel(a[0], mu_ref) < 1e-9 and rel(a[1], cov_ref) < 1e-9
     assert rel(a[0], b[0]) < 1e-12 and rel(a[1], b[1]) < 1e-12
     assert np.array_equal(a[2], a[0][-1]) and np.array_equal(a[3], a[1][-1])
+
+
+@pytest.mark.parametrize("lpt", [3, 4, 8])
+def test_owner_ladder_issues_one_broadcast_from_lane_k_over_R(quad_lib, lpt):
+    """fk_owner.hpp's owner_value<R, LPT> -- the ladder every several-lane kernel reaches row k's owner through -- over an exchange
+    object that records its bcast<O> calls: for every R in 1..6 and every row slot k of the LPT lanes, exactly one broadcast, from
+    lane k / R (the last lane's clamped tail slots included: the ladder is over the owning lane, not the row), handing the value back."""
+    for R in range(1, 7):
+        for k in range(lpt * R):
+            n, out, v = ctypes.c_int(-1), ctypes.c_double(np.nan), 1.5 + k
+            lane = quad_lib.hc_owner_value(ctypes.c_int(lpt), ctypes.c_int(R), ctypes.c_int(k), ctypes.c_double(v),
+                                           ctypes.byref(n), ctypes.byref(out))
+            assert (lane, n.value, out.value) == (k // R, 1, v), (lpt, R, k)
+
+
+def test_owner_row_reads_the_owners_slot_of_every_row(quad_lib):
+    """FK_OWNER_ROW with four lanes, R = 3, NX = 10: row k comes from lane k / R -- 0, 0, 0, 1, 1, 1, 2, 2, 2, 3 -- as that lane's
+    slot k % R, one broadcast per element."""
+    lane, n, slot = ((ctypes.c_int * 10)(), (ctypes.c_int * 10)(), (ctypes.c_int * 10)())
+    quad_lib.hc_owner_row_4_3_10(lane, n, slot)
+    assert list(lane) == [0, 0, 0, 1, 1, 1, 2, 2, 2, 3]
+    assert list(n) == [10] * 10
+    assert list(slot) == [k % 3 for k in range(10)]
