@@ -81,6 +81,9 @@ SIGNATURES = {
     "fk_ckf_linear_batch_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 15),
     "fk_ckf_linear_predict_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 7),
     "fk_ckf_linear_update_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 13),
+    "fk_ekf_predict_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 8),
+    "fk_ekf_update_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 13),
+    "fk_ekf_step_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 19),
     "fk_enkf_workspace_bytes": (c_sz, [c_i32, c_i32, c_i64]),
     "fk_enkf_predict_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 7 + [c_sz, c_vp, c_vp]),
     "fk_enkf_update_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 13 + [c_sz, c_vp, c_vp]),

@@ -284,6 +284,35 @@ def ckf_linear_update(desc_kw, H, R, z, x, P, points, *, mask=None, y=None, K=No
     _abi.check(rc, "fk_ckf_linear_update_f64")
 
 
+def ekf_predict(desc_kw, F, Q, x, P, *, B=None, u=None, status=None):
+    """fk_ekf_predict_f64: x = F x + B u, P = F P F' + Q for every track; F, Q, B shared or per track (desc model_mode)"""
+    d = fk_kf_desc(**desc_kw)
+    rc = _abi.lib().fk_ekf_predict_f64(d, _ptr(F), _ptr(Q), _ptr(B), _ptr(u), _ptr(x), _ptr(P), _ptr(status), _stream())
+    _abi.check(rc, "fk_ekf_predict_f64")
+
+
+def ekf_update(desc_kw, H, R, y, x, P, *, mask=None, K=None, S=None, SI=None, log_likelihood=None, mahalanobis=None,
+               status=None):
+    """fk_ekf_update_f64: the extended filter's update with each track's Jacobian H [N][m*n] and innovation y [N][m] given"""
+    _keep = []
+    d = fk_kf_desc(**desc_kw)
+    rc = _abi.lib().fk_ekf_update_f64(d, _ptr(H), _ptr(R), _ptr(y), _mask_ptr(mask, _keep), _ptr(x), _ptr(P), _ptr(K), _ptr(S),
+                                      _ptr(SI), _ptr(log_likelihood), _ptr(mahalanobis), _ptr(status), _stream())
+    _abi.check(rc, "fk_ekf_update_f64")
+
+
+def ekf_step(desc_kw, H, R, y, F, Q, x, P, *, mask=None, B=None, u=None, x_post=None, P_post=None, K=None, S=None, SI=None,
+             log_likelihood=None, mahalanobis=None, status=None):
+    """fk_ekf_step_f64: that update, then the predict of the next step, in one launch; x, P leave as the next prior, the
+    posterior goes to x_post / P_post"""
+    _keep = []
+    d = fk_kf_desc(**desc_kw)
+    rc = _abi.lib().fk_ekf_step_f64(d, _ptr(H), _ptr(R), _ptr(y), _mask_ptr(mask, _keep), _ptr(F), _ptr(Q), _ptr(B), _ptr(u),
+                                    _ptr(x), _ptr(P), _ptr(x_post), _ptr(P_post), _ptr(K), _ptr(S), _ptr(SI),
+                                    _ptr(log_likelihood), _ptr(mahalanobis), _ptr(status), _stream())
+    _abi.check(rc, "fk_ekf_step_f64")
+
+
 ENKF_CHUNK = 2048         # members per workgroup and per slab of partial sums (csrc/fk_enkf.hpp: ENKF_CHUNK)
 
 

@@ -362,6 +362,39 @@ int fk_ckf_linear_update_f64(const fk_kf_desc *desc, const double *H, const doub
                              double *x, double *P, const double *points, double *y, double *K, double *S, double *SI,
                              int32_t *status, void *stream);
 
+/* ExtendedKalmanFilter (filterpy/kalman/EKF.py) for N independent filters, one time step per call: the Jacobian
+ * H = HJacobian(x) and the innovation y = residual(z, Hx(x)) of a step are formed by the caller (they are what is nonlinear)
+ * and arrive as records of the track; nothing here forms z - H x.
+ *   desc      : n (1..16), m (1..8), nu, N, layout; model_mode FK_MODEL_SHARED (F [n*n], Q [n*n], R [m*m], B [n*nu] shared) or
+ *               FK_MODEL_PER_TRACK (F, Q [N][n*n], R [N][m*m], B [N][n*nu]: records in `layout`); flags 0 or
+ *               FK_KF_FLAG_R_JOSEPH_DIAG (as for fk_kf_update_f64); alpha_sq 1, update_first 0 -- anything else, the per-step
+ *               model modes included, FK_ERR_UNSUPPORTED.  T is ignored.
+ *   H [N][m*n], y [N][m], x [N][n], P [N][n*n], u [N][nu] (NULL when nu == 0): records in `layout`.
+ *   mask      : uint8 [N], 0 = no measurement (update(None), :297-301): the update leaves x and P of that track as they are and
+ *               writes none of its by-products; NULL = every track updates.
+ *   status [N] or NULL: FK_STATUS_NOT_PD (a pivot of the L D L' of S that is not > 0), FK_STATUS_NONFINITE.
+ * The exact shapes of csrc/fk_dims_ekf.def run unrolled in registers, every other size a padded general kernel.
+ *
+ * fk_ekf_predict_f64 (:351, :367): x = F x + B u;  P = F P F' + Q. */
+int fk_ekf_predict_f64(const fk_kf_desc *desc, const double *F, const double *Q, const double *B, const double *u, double *x,
+                       double *P, int32_t *status, void *stream);
+
+/* ExtendedKalmanFilter.update (:319-332) with H and y given: S = H P H' + R;  K = P H' inv(S) (in-lane L D L');  x += K y;
+ * P = (I - K H) P (I - K H)' + K R K'.  By-products of the tracks that update, each may be NULL: K [N][n*m], S, SI [N][m*m],
+ * log_likelihood [N] = log N(y; 0, S) (:380), mahalanobis [N] = sqrt(y' SI y) (:409). */
+int fk_ekf_update_f64(const fk_kf_desc *desc, const double *H, const double *R, const double *y, const uint8_t *mask, double *x,
+                      double *P, double *K, double *S, double *SI, double *log_likelihood, double *mahalanobis,
+                      int32_t *status, void *stream);
+
+/* The update of step k (:319-332) and the predict of step k + 1 (:351, :367) in ONE launch, bit-identical to
+ * fk_ekf_update_f64 followed by fk_ekf_predict_f64: x and P cross device memory once per step.  x_post [N][n],
+ * P_post [N][n*n] (each may be NULL) receive the posterior; on exit x, P hold the prior of the next step.  A masked track
+ * is still predicted. */
+int fk_ekf_step_f64(const fk_kf_desc *desc, const double *H, const double *R, const double *y, const uint8_t *mask,
+                    const double *F, const double *Q, const double *B, const double *u, double *x, double *P, double *x_post,
+                    double *P_post, double *K, double *S, double *SI, double *log_likelihood, double *mahalanobis,
+                    int32_t *status, void *stream);
+
 /* EnsembleKalmanFilter (filterpy/kalman/ensemble_kalman_filter.py:218-290): ONE filter whose state is an ensemble of N members,
  * sigmas [N][n] in `layout`.  The parallelism is over the members; the means and covariances are reductions over all of them,
  * summed in a fixed order (per workgroup of 2048 members, then over the workgroups in index order by a second launch): the
