@@ -12,8 +12,10 @@
 // corrected by the shifted mean in the finalize:
 //     sum (a - mean a)(b - mean b)' = sum da db' - (sum da)(sum db)' / N,     da = a - pa, db = b - pb.
 // The pivots are the incoming x (update), F x or x (predict) and H x or member 0's h: as close to the mean as the spread of
-// the ensemble, so the correction term is of the size of the result and costs no digits (the uncentred sum s s' - N x x'
-// loses |x|^2 / var of them).  The update's centre of the members IS self.x, as in the reference (:256-257), so there the
+// the ensemble -- member 0 as close as ONE member is -- so the correction term is of the size of the result and costs no
+// digits (the uncentred sum s s' - N x x' loses |x|^2 / var of them).  A pivot d spreads from the mean costs eps d^2: with
+// member 0 at d = 30, S, SI, K and P are 100-210 x less accurate than the two-pass form and still 0.05 of the precision bar
+// (tests/test_host_enkf_hp.py, tests/test_gpu_enkf_precision.py: the pivot contract).  The update's centre of the members IS self.x, as in the reference (:256-257), so there the
 // member pivot is not a device but the definition.
 //
 // Accumulators per lane (NX, NZ the register shapes):

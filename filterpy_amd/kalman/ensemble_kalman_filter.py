@@ -41,7 +41,9 @@ Divergences:
     reference inverts whatever it gets;
   * dim_x > 16 or dim_z > 8 is refused (the kernels' compiled range);
   * the sums are taken in the kernels' order and every second moment is a one-pass sum of pivot-shifted products: x, P, K, S
-    and the members agree with the reference to rounding (1e-10 relative at a mean 1e3 spreads away from 0).
+    and the members agree with the reference to rounding (1e-10 relative at a mean 1e3 spreads away from 0; against a longdouble
+    truth, within 5 x the reference's own error at a mean 1e4 spreads away and on stiff models: docs/MEASUREMENTS.md,
+    "EnKF precision").
 Out of scope: a bank of several ensembles (n_tracks); a one-launch batch_filter -- it would need workgroups to wait for each
 other inside a launch, and a step is already a short chain of launches on the caller's stream; multi-GPU.
 """
@@ -271,7 +273,8 @@ class EnsembleKalmanFilter(object):
         if F is None:
             self._sig = moved if isinstance(moved, torch.Tensor) else self._records(moved, n)
         # the pivot of the one-pass sums: with a matrix the kernel takes F x; behind a callable the mean may have moved by
-        # many spreads, and member 0 as fx left it is within one of the new mean
+        # many spreads, and member 0 as fx left it is as close to the new mean as one member is (d spreads away it costs
+        # eps d^2: at d = 30 the prior P is 2.8 x the two-pass form's error, tests/test_gpu_enkf_precision.py)
         if F is None:
             x = self._members()[0].clone()
         else:

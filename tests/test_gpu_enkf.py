@@ -2,9 +2,10 @@
 both layouts, ensemble sizes around every boundary of the kernels against tests/enkf_port.py, bit-identity, the offset case
 that tells a centred kernel from an uncentred one, the factor path, noise="device", and the refusals.
 
-Status: written against the kernels as built for gfx950, not yet run on an MI355X -- no GPU was to be had while the feature was
-built (docs/MEASUREMENTS.md "EnKF").  The same arithmetic (csrc/fk_enkf.hpp compiled for the host, driven
-in the kernels' order) passes the same comparisons at 1e-10 in tests/test_host_enkf.py."""
+Status: all 73 cases pass on the MI355X as written (first hardware run: worst error against the port 1.1e-13, (16,8) at N = 2;
+1e-15 ... 1e-14 elsewhere).  The same arithmetic (csrc/fk_enkf.hpp compiled for the host, driven in the kernels' order) passes the
+same comparisons at 1e-10 in tests/test_host_enkf.py; tests/test_gpu_enkf_precision.py holds the kernels to a longdouble truth on
+hard ensembles, where 1e-10 against a float64 port on benign models would not see four lost digits."""
 import os
 import subprocess
 import sys

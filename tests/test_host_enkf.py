@@ -1,9 +1,7 @@
 """The ensemble Kalman filter on the CPU: tests/enkf_port.py against the goldens frozen from the live reference, the member /
 slab / finalize arithmetic of filterpy_amd/csrc/fk_enkf.hpp compiled for the host and driven chunk by chunk in the kernels'
 order, and the drop-in layer (EnsembleKalmanFilter) on a stand-in engine."""
-import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,6 +9,8 @@ import pytest
 from conftest import ROOT, rel_err
 import enkf_port as ep
 import enkf_cases as ec
+import enkf_host
+from enkf_host import EXACT, hc_predict, hc_update
 import fake_enkf_engine
 from filterpy_amd.kalman import EnsembleKalmanFilter
 
@@ -56,202 +56,11 @@ def test_port_one_pass_forms_agree_where_the_data_is_centred():
         assert rel_err(ep.moments(a, a.mean(0), b, b.mean(0), mode, a[0], b[0]), want) <= 1e-13
 
 
-# ---- fk_enkf.hpp compiled for the host ---------------------------------------------------------------------------------------
-HC_SRC = r'''
-#include <vector>
-#include "fk_enkf.hpp"
-using namespace fk;
-#ifndef HC_NX
-#define HC_NX 16
-#define HC_NZ 8
-#endif
-constexpr int NX = HC_NX, NZ = HC_NZ;
-extern "C" int hc_chunk() { return ENKF_CHUNK; }
-extern "C" long hc_workspace_doubles(long N) { return enkf_workspace_doubles(N); }
-
-static void pad(double *dst, int ROWS, int COLS, const double *src, int r, int c, double diag)
-{
-    for (int a = 0; a < ROWS; ++a)
-        for (int b = 0; b < COLS; ++b) dst[a * COLS + b] = (src && a < r && b < c) ? src[a * c + b] : (a == b ? diag : 0.0);
-}
-template <int D> static void load(double (&v)[D], const double *base, long i, int d) { for (int e = 0; e < D; ++e) v[e] = e < d ? base[i * d + e] : 0.0; }
-template <int D> static void store(const double (&v)[D], double *base, long i, int d) { for (int e = 0; e < d; ++e) base[i * d + e] = v[e]; }
-
-// the workgroup's tree: a butterfly over each wave of 64 lanes, then the four waves in order
-template <int A> static void block_sum(std::vector<double> &lanes, double *slab)
-{
-    std::vector<double> t(64);
-    for (int e = 0; e < A; ++e) {
-        double w[4];
-        for (int wave = 0; wave < 4; ++wave) {
-            for (int off = 32; off >= 1; off >>= 1) {
-                for (int l = 0; l < 64; ++l) t[l] = lanes[(wave * 64 + l) * A + e] + lanes[(wave * 64 + (l ^ off)) * A + e];
-                for (int l = 0; l < 64; ++l) lanes[(wave * 64 + l) * A + e] = t[l];
-            }
-            w[wave] = lanes[(wave * 64) * A + e];
-        }
-        slab[e] = ((w[0] + w[1]) + w[2]) + w[3];
-    }
-}
-// one pass: member(i, acc of the lane that owns member i) for every member in the kernels' order, one slab per chunk
-template <int A, class Member> static void pass(long N, double *slabs, Member member)
-{
-    for (long c = 0; c < enkf_slabs(N); ++c) {
-        std::vector<double> lanes((size_t)ENKF_BLOCK * A, 0.0);
-        for (int l = 0; l < ENKF_BLOCK; ++l)
-            for (int j = 0; j < ENKF_PER_LANE; ++j) {
-                const long i = c * ENKF_CHUNK + (long)j * ENKF_BLOCK + l;
-                if (i < N) member(i, *reinterpret_cast<double (*)[A]>(&lanes[(size_t)l * A]));
-            }
-        block_sum<A>(lanes, slabs + c * ENKF_SLAB);
-    }
-}
-static void totals(const double *slabs, long N, int A, double *tot)
-{
-    std::vector<double> runs((size_t)ENKF_GROUPS * ENKF_SLAB);
-    for (int g = 0; g < ENKF_GROUPS; ++g)
-        for (int e = 0; e < A; ++e) runs[g * ENKF_SLAB + e] = enkf_run_sum(slabs, enkf_slabs(N), e, g);
-    for (int e = 0; e < A; ++e) tot[e] = enkf_total(runs.data(), ENKF_SLAB, e);
-}
-
-extern "C" int hc_predict(int n, long N, const double *F, const double *noise, const double *factor, double *sig, double *x, double *P,
-                          double *ws)
-{
-    if (n > NX) return -1;
-    using Acc = EnkfPredictAcc<NX>;
-    double Fp[NX * NX], fp[NX * NX], piv[NX];
-    pad(Fp, NX, NX, F, n, n, 1.0);
-    pad(fp, NX, NX, factor, n, n, 0.0);
-    for (int i = 0; i < NX; ++i) {
-        double xs[NX];
-        for (int j = 0; j < NX; ++j) xs[j] = j < n ? x[j] : 0.0;
-        double p = xs[i];
-        if (F) { p = Fp[i * NX] * xs[0]; for (int j = 1; j < NX; ++j) p = fma(Fp[i * NX + j], xs[j], p); }
-        piv[i] = p;
-    }
-    double *slabs = ws + ENKF_WS_SLABS;
-    pass<Acc::SIZE>(N, slabs, [&](long i, double (&acc)[Acc::SIZE]) {
-        double s[NX], w[NX], e[NX];
-        load<NX>(s, sig, i, n); load<NX>(w, noise, i, n);
-        enkf_draw<NX>(w, factor ? fp : nullptr, e);
-        enkf_predict_member<NX>(s, e, F ? Fp : nullptr, piv, acc);
-        store<NX>(s, sig, i, n);
-    });
-    double tot[ENKF_SLAB];
-    totals(slabs, N, Acc::SIZE, tot);
-    for (int i = 0; i < n; ++i) x[i] = enkf_mean(piv[i], tot[i], N);
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j) {
-            const int hi = i > j ? i : j, lo = i > j ? j : i;
-            P[i * n + j] = enkf_cov(tot[NX + enkf_tri(hi, lo)], tot[hi], tot[lo], N);
-        }
-    return 0;
-}
-
-extern "C" int hc_update(int n, int m, long N, const double *H, const double *sigmas_h, const double *R, const double *z,
-                         const double *noise, const double *factor, double *sig, double *x, double *P, double *S, double *SI,
-                         double *K, double *ws)
-{
-    if (n > NX || m > NZ) return -1;
-    using Acc = EnkfStatsAcc<NX, NZ>;
-    double Hp[NZ * NX], fp[NZ * NZ], px[NX], ph[NZ], zp[NZ];
-    pad(Hp, NZ, NX, H, m, n, 0.0);
-    pad(fp, NZ, NZ, factor, m, m, 0.0);
-    for (int i = 0; i < NX; ++i) px[i] = i < n ? x[i] : 0.0;
-    for (int c = 0; c < NZ; ++c) {
-        zp[c] = c < m ? z[c] : 0.0;
-        double p = 0.0;
-        if (H) { p = Hp[c * NX] * px[0]; for (int j = 1; j < NX; ++j) p = fma(Hp[c * NX + j], px[j], p); }
-        else if (c < m) p = sigmas_h[c];
-        ph[c] = p;
-    }
-    auto h_of = [&](const double (&s)[NX], long i, double (&h)[NZ]) {
-        if (H) enkf_matvec<NZ, NX>(Hp, s, h); else load<NZ>(h, sigmas_h, i, m);
-    };
-    double *slabs = ws + ENKF_WS_SLABS;
-    pass<Acc::SIZE>(N, slabs, [&](long i, double (&acc)[Acc::SIZE]) {
-        double s[NX], h[NZ];
-        load<NX>(s, sig, i, n);
-        h_of(s, i, h);
-        enkf_stats_member<NX, NZ>(s, h, px, ph, acc);
-    });
-    double tot[ENKF_SLAB], pxz[NX * NZ], Kp[NX * NZ];
-    totals(slabs, N, Acc::SIZE, tot);
-    for (int r = 0; r < m; ++r)
-        for (int c = 0; c < m; ++c) {
-            const int hi = r > c ? r : c, lo = r > c ? c : r;
-            S[r * m + c] = enkf_cov(tot[Acc::OFF_HH + enkf_tri(hi, lo)], tot[Acc::OFF_H + hi], tot[Acc::OFF_H + lo], N) + R[hi * m + lo];
-        }
-    for (int i = 0; i < n; ++i)
-        for (int c = 0; c < m; ++c) pxz[i * m + c] = enkf_cov(tot[Acc::OFF_SH + i * NZ + c], tot[i], tot[Acc::OFF_H + c], N);
-    const int st = enkf_spd_inverse(S, m, SI);
-    for (int i = 0; i < n; ++i)
-        for (int c = 0; c < m; ++c) K[i * m + c] = enkf_gain_entry(pxz, SI, m, i, c);
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j) P[i * n + j] -= enkf_ksk_entry(K, S, m, i, j);
-    pad(Kp, NX, NZ, K, n, m, 0.0);
-    pass<NX>(N, slabs, [&](long i, double (&acc)[NX]) {
-        double s[NX], h[NZ], w[NZ], e[NZ];
-        load<NX>(s, sig, i, n);
-        h_of(s, i, h);
-        load<NZ>(w, noise, i, m);
-        enkf_draw<NZ>(w, factor ? fp : nullptr, e);
-        enkf_apply_member<NX, NZ>(s, h, e, zp, Kp, px, acc);
-        store<NX>(s, sig, i, n);
-    });
-    totals(slabs, N, NX, tot);
-    for (int i = 0; i < n; ++i) x[i] = enkf_mean(px[i], tot[i], N);
-    return st;
-}
-'''
-EXACT = [(2, 1), (4, 2)]
-
-
+# ---- fk_enkf.hpp compiled for the host (the driver and its builds: tests/enkf_host.py) -----------------------------------------
 @pytest.fixture(scope="module")
 def hc(tmp_path_factory):
-    """the padded (16, 8) build (what the general kernel runs) and exact builds of two fast shapes"""
-    d = tmp_path_factory.mktemp("hc_enkf")
-    src = d / "hc_enkf.cpp"
-    src.write_text(HC_SRC)
-    libs = {}
-    for dims in [None] + EXACT:
-        so = d / ("libhc_enkf%s.so" % ("" if dims is None else "_%d_%d" % dims))
-        defs = [] if dims is None else ["-DHC_NX=%d" % dims[0], "-DHC_NZ=%d" % dims[1]]
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=on", "-w", *defs,
-                               "-I", os.path.join(ROOT, "filterpy_amd", "csrc"), str(src), "-o", str(so)])
-        lib = ctypes.CDLL(str(so))
-        lib.hc_workspace_doubles.restype = ctypes.c_long
-        libs[dims] = lib
-    return libs
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-
-
-def _cc(a):
-    return None if a is None else np.ascontiguousarray(a, dtype=float)
-
-
-def hc_predict(lib, sig, x, e, F=None, factor=None):
-    N, n = sig.shape
-    sig, x, P = _cc(sig).copy(), _cc(x).copy(), np.zeros((n, n))
-    ws = np.zeros(lib.hc_workspace_doubles(ctypes.c_long(N)))
-    F, e, factor = _cc(F), _cc(e), _cc(factor)
-    assert lib.hc_predict(n, ctypes.c_long(N), _p(F), _p(e), _p(factor), _p(sig), _p(x), _p(P), _p(ws)) == 0
-    return sig, x, P
-
-
-def hc_update(lib, sig, x, P, z, R, e, H=None, sigmas_h=None, factor=None):
-    N, n = sig.shape
-    m = len(z)
-    sig, x, P = _cc(sig).copy(), _cc(x).copy(), _cc(P).copy()
-    S, SI, K = np.zeros((m, m)), np.zeros((m, m)), np.zeros((n, m))
-    ws = np.zeros(lib.hc_workspace_doubles(ctypes.c_long(N)))
-    H, sigmas_h, R, z, e, factor = _cc(H), _cc(sigmas_h), _cc(R), _cc(z), _cc(e), _cc(factor)
-    st = lib.hc_update(n, m, ctypes.c_long(N), _p(H), _p(sigmas_h), _p(R), _p(z), _p(e), _p(factor), _p(sig), _p(x), _p(P), _p(S),
-                       _p(SI), _p(K), _p(ws))
-    return sig, x, P, K, S, SI, st
+    """the padded (16, 8) build (what the general kernel runs) and the exact builds of the fast shapes (tests/enkf_host.py)"""
+    return enkf_host.libs(tmp_path_factory)
 
 
 class HostFilter(ep.Port):
