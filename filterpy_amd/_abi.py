@@ -87,6 +87,8 @@ SIGNATURES = {
     "fk_enkf_workspace_bytes": (c_sz, [c_i32, c_i32, c_i64]),
     "fk_enkf_predict_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 7 + [c_sz, c_vp, c_vp]),
     "fk_enkf_update_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 13 + [c_sz, c_vp, c_vp]),
+    "fk_enkf_bank_predict_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc), c_i64] + [c_vp] * 8),
+    "fk_enkf_bank_update_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc), c_i64] + [c_vp] * 15),
     "fk_ut_sigma_points_f64": (ctypes.c_int, [c_i32, c_i64, c_i32, c_f64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "fk_ut_transform_f64": (ctypes.c_int, [c_i32, c_i32, c_i64, c_i32] + [c_vp] * 7),
     "fk_ut_cross_variance_f64": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i64, c_i32] + [c_vp] * 7),

@@ -341,6 +341,27 @@ def enkf_update(desc_kw, R, z, noise, sigmas, x, P, workspace, *, H=None, sigmas
     _abi.check(rc, "fk_enkf_update_f64")
 
 
+def enkf_bank_predict(desc_kw, n_tracks, noise, sigmas, x, P, *, F=None, factor=None, status=None):
+    """fk_enkf_bank_predict_f64: the predict of n_tracks ensembles of desc N <= ENKF_CHUNK members in one launch; F and factor
+    shared or one per ensemble (desc model_mode); status [n_tracks] int32"""
+    d = fk_kf_desc(**desc_kw)
+    rc = _abi.lib().fk_enkf_bank_predict_f64(d, int(n_tracks), _ptr(F), _ptr(noise), _ptr(factor), _ptr(sigmas), _ptr(x), _ptr(P),
+                                             _ptr(status), _stream())
+    _abi.check(rc, "fk_enkf_bank_predict_f64")
+
+
+def enkf_bank_update(desc_kw, n_tracks, R, z, noise, sigmas, x, P, *, H=None, sigmas_h=None, mask=None, factor=None, S=None,
+                     SI=None, K=None, status=None):
+    """fk_enkf_bank_update_f64: the update of n_tracks ensembles in one launch; mask [n_tracks] uint8 (0: the ensemble is left
+    as it is); include/filterhip.h"""
+    _keep = []
+    d = fk_kf_desc(**desc_kw)
+    rc = _abi.lib().fk_enkf_bank_update_f64(d, int(n_tracks), _ptr(H), _ptr(sigmas_h), _ptr(R), _ptr(z), _mask_ptr(mask, _keep),
+                                            _ptr(noise), _ptr(factor), _ptr(sigmas), _ptr(x), _ptr(P), _ptr(S), _ptr(SI), _ptr(K),
+                                            _ptr(status), _stream())
+    _abi.check(rc, "fk_enkf_bank_update_f64")
+
+
 def ut_sigma_points(n, N, layout, scale, x, P, sigmas, status=None):
     rc = _abi.lib().fk_ut_sigma_points_f64(n, N, LAYOUTS[layout], float(scale), _ptr(x), _ptr(P),
                                            _ptr(sigmas), _ptr(status), _stream())

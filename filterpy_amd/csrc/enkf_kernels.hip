@@ -25,30 +25,11 @@
 #endif
 #include "fk_device.hpp"
 #include "fk_enkf.hpp"
+#include "fk_enkf_dev.hpp"
 
 namespace fk {
 
 static_assert(ENKF_BLOCK == BLOCK, "four waves per workgroup");
-
-// element e of member i's record: [d][N] element-major, [N][d] NumPy order (64-bit indices: no 4 GiB limit on the ensemble)
-template <int LAYOUT>
-__device__ __forceinline__ long enkf_at(long i, int e, long N, int d)
-{
-    return LAYOUT == LAYOUT_SOA ? (long)e * N + i : i * d + e;
-}
-
-template <int D, int LAYOUT, bool EXACT>
-__device__ __forceinline__ void enkf_load(double (&v)[D], const double *__restrict__ base, long i, long N, int d)
-{
-    FK_UNROLL for (int e = 0; e < D; ++e) v[e] = (EXACT || e < d) ? base[enkf_at<LAYOUT>(i, e, N, EXACT ? D : d)] : 0.0;
-}
-
-template <int D, int LAYOUT, bool EXACT>
-__device__ __forceinline__ void enkf_store(const double (&v)[D], double *__restrict__ base, long i, long N, int d)
-{
-    FK_UNROLL for (int e = 0; e < D; ++e)
-        if (EXACT || e < d) base[enkf_at<LAYOUT>(i, e, N, EXACT ? D : d)] = v[e];
-}
 
 // a ROWS x COLS matrix in LDS from an r x c one in global memory (NULL: padding only); the caller synchronises
 template <int ROWS, int COLS>
@@ -58,22 +39,6 @@ __device__ __forceinline__ void enkf_fill(double *dst, const double *__restrict_
         const int a = (int)k / COLS, b = (int)k % COLS;
         dst[k] = (src != nullptr && a < r && b < c) ? src[a * c + b] : ((a == b) ? diag_pad : 0.0);
     }
-}
-
-// The workgroup's sum of every accumulator, in a fixed tree, into its slab: a butterfly over the 64 lanes of a wave (every
-// lane ends with the wave's sum), then the four waves in index order.  red: [4][A] doubles of LDS.
-template <int A>
-__device__ __forceinline__ void enkf_block_sum(double (&acc)[A], double *red, double *__restrict__ slab)
-{
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    FK_UNROLL for (int e = 0; e < A; ++e) {
-        double v = acc[e];
-        FK_UNROLL for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-        if (lane == 0) red[wave * A + e] = v;
-    }
-    __syncthreads();
-    for (unsigned e = threadIdx.x; e < (unsigned)A; e += ENKF_BLOCK)
-        slab[e] = ((red[e] + red[A + e]) + red[2 * A + e]) + red[3 * A + e];
 }
 
 // ---- predict -----------------------------------------------------------------------------------------------------------

@@ -171,10 +171,12 @@ FK_HD double enkf_cov(double sab, double sa, double sb, long N)
 
 // SI = S^-1 for the m x m S (row-major, stride m; its lower triangle is read) by the refined-pivot L D L' of fk_ukf.hpp,
 // padded to 8 x 8 with the identity.  Returns ST_NOT_PD when a pivot is at or below m eps max|diag S| (or is not a number).
-FK_HD int enkf_spd_inverse(const double *S, int m, double *SI)
+// L, d, dinv, X: the work arrays, wherever the caller keeps them (the bank kernels of enkf_bank.hip: in LDS, so that the one
+// lane that runs this holds none of the 144 doubles in scratch memory).
+FK_HD int enkf_spd_inverse_in(const double *S, int m, double *SI, double (&L)[ENKF_MAXZ * ENKF_MAXZ], double (&d)[ENKF_MAXZ],
+                              double (&dinv)[ENKF_MAXZ], double (&X)[ENKF_MAXZ * ENKF_MAXZ])
 {
     constexpr int M = ENKF_MAXZ;
-    double L[M * M], d[M], dinv[M], X[M * M];
     double dmax = 0.0;
     for (int a = 0; a < M; ++a)
         for (int b = 0; b < M; ++b) {
@@ -193,6 +195,13 @@ FK_HD int enkf_spd_inverse(const double *S, int m, double *SI)
     for (int a = 0; a < m; ++a)
         for (int b = 0; b <= a; ++b) SI[a * m + b] = SI[b * m + a] = X[a * M + b];
     return st;
+}
+
+FK_HD int enkf_spd_inverse(const double *S, int m, double *SI)
+{
+    constexpr int M = ENKF_MAXZ;
+    double L[M * M], d[M], dinv[M], X[M * M];
+    return enkf_spd_inverse_in(S, m, SI, L, d, dinv, X);
 }
 
 // K[i][c] = sum_a Pxz[i][a] SI[a][c]   (dot(P_xz, SI), :261)
@@ -225,6 +234,18 @@ struct EnkfArgs {
     int32_t *status;
     long N;
     int n, m, phase, ax, az;
+};
+
+// What the bank kernels (enkf_bank.hip) take: B ensembles of N <= ENKF_CHUNK members each, one contiguous block per ensemble
+// ([B][d][N] or [B][N][d]); x [B][n], P [B][n*n], K [B][n*m], S, SI [B][m*m], z [B][m], mask, status [B]; F, H, R and the
+// factor once (per_track 0) or once per ensemble.
+struct EnkfBankArgs {
+    const double *F, *H, *sigmas_h, *R, *z, *noise, *factor;
+    const uint8_t *mask;
+    double *sigmas, *x, *P, *S, *SI, *K;
+    int32_t *status;
+    long B, N;
+    int n, m, per_track, update;
 };
 
 }  // namespace fk

@@ -423,6 +423,23 @@ int fk_enkf_update_f64(const fk_kf_desc *desc, const double *H, const double *si
                        const double *noise, const double *factor, double *sigmas, double *x, double *P, double *S, double *SI,
                        double *K, void *workspace, size_t workspace_bytes, int32_t *status, void *stream);
 
+/* A BANK of n_ensembles ensemble Kalman filters of desc->N members each, 2 <= N <= 2048: one launch per call for all of them
+ * (one wave per ensemble for N <= 64, one workgroup per ensemble above).  Every ensemble occupies one contiguous block:
+ * sigmas [B][N][n] records -- 'soa' [B][n][N], so slice b is the single call's (n, N) array; 'aos' [B][N][n] --, noise and
+ * sigmas_h likewise with d = n or m.  x [B][n], P [B][n*n], K [B][n*m], S, SI [B][m*m], z [B][m], row-major per ensemble.
+ *   desc      : as above, except model_mode FK_MODEL_SHARED (F, H, R, factor given once) or FK_MODEL_PER_TRACK (one per
+ *               ensemble: F [B][n*n], H [B][m*n], R [B][m*m], factor [B][d*d]).  N > 2048 is FK_ERR_UNSUPPORTED.
+ *   mask      : [B] bytes or NULL; 0 makes the update of that ensemble a no-op (members, x, P, K, S, SI untouched, status 0).
+ *   status    : [B] int32 (or NULL), per ensemble as above.
+ * The arithmetic and its order are those of fk_enkf_predict_f64 / fk_enkf_update_f64: ensemble b's results are bit-identical
+ * to the single call on slice b.  No workspace; nothing is kept between calls. */
+int fk_enkf_bank_predict_f64(const fk_kf_desc *desc, int64_t n_ensembles, const double *F, const double *noise,
+                             const double *factor, double *sigmas, double *x, double *P, int32_t *status, void *stream);
+int fk_enkf_bank_update_f64(const fk_kf_desc *desc, int64_t n_ensembles, const double *H, const double *sigmas_h,
+                            const double *R, const double *z, const uint8_t *mask, const double *noise, const double *factor,
+                            double *sigmas, double *x, double *P, double *S, double *SI, double *K, int32_t *status,
+                            void *stream);
+
 /* ------------------------------------------------------------------ */
 /* Unscented transform path                                           */
 /* ------------------------------------------------------------------ */

@@ -11,6 +11,17 @@ For context only, the LIVE reference's seconds per step at N = 1e4 where a check
 never to be read as a ratio of like things.  One JSON line per row; --out writes them.
 
     python tools/bench_enkf.py [--reps 10] [--members 1048576 8388608] [--out profiles/enkf/bench.json]
+
+--bank measures EnsembleKalmanFilterBank's two launches (fk_enkf_bank_predict_f64 / fk_enkf_bank_update_f64,
+csrc/enkf_bank.hip) against what the library offered for the same job before: a Python loop over B EnsembleKalmanFilter objects
+with matrix fx / hx and noise="device".  Rows: B tracks x N members at (4, 2) and (6, 3), one predict + update cycle, element-major
+records.  Per row: the bank's kernel time (HIP events around its two launches), the algorithmic bytes of the cycle -- predict
+3 N n doubles per track, update (2 n + m) N on the one-wave route (N <= 64: the member stays in registers) and (3 n + m) N above
+-- and their fraction of 8 TB/s; for the loop its launches alone (the six launches per track issued back to back on the slices of
+the same arrays, no host synchronisation; HIP events) and the class loop's wall time, which is what a user pays: every
+predict() / update() of the single class downloads x, P, K, S.  The class loop runs --loop-reps times (once at B >= 10000).
+
+    python tools/bench_enkf.py --bank [--tracks 100 1000 10000] [--sizes 32 64 256 1024] [--out profiles/enkf/bank_bench.json]
 """
 import argparse
 import json
@@ -60,12 +71,117 @@ def reference_row(N=10000, steps=3):
                 note="live reference on one CPU core: context, not a ratio of like things")
 
 
+def _events(fn, reps, before=None):
+    import torch
+    ms = []
+    for _ in range(reps):
+        if before:
+            before()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return ms
+
+
+def bank_rows(a):
+    import torch
+    from filterpy_amd import _engine as E
+    from filterpy_amd.kalman import EnsembleKalmanFilter
+    from filterpy_amd.kalman.ensemble_kalman_filter import _factor
+    torch.cuda.set_device(0)
+    rows, layout = [], "soa"
+    for n, m in [(4, 2), (6, 3)]:
+        F, H, Q, R = model(n, m)
+        dF, dH, dR, AQ, AR = (E.dev(v) for v in (F, H, R, _factor(Q), _factor(R)))
+        for B in a.tracks:
+            for N in a.sizes:
+                desc = dict(n=n, m=m, nu=0, model_mode=0, N=N, T=1, layout=E.LAYOUTS[layout], update_first=0, alpha_sq=1.0, flags=0)
+                sig = torch.randn((B, n, N), dtype=torch.float64, device="cuda")
+                w1, w2 = torch.randn((B, n, N), dtype=torch.float64, device="cuda"), torch.randn((B, m, N), dtype=torch.float64, device="cuda")
+                x, P = torch.zeros((B, n), dtype=torch.float64, device="cuda"), torch.eye(n, dtype=torch.float64, device="cuda").repeat(B, 1, 1)
+                S, SI, K = (torch.empty((B,) + s, dtype=torch.float64, device="cuda") for s in ((m, m), (m, m), (n, m)))
+                z = torch.zeros((B, m), dtype=torch.float64, device="cuda")
+                st = torch.zeros(B, dtype=torch.int32, device="cuda")
+                ws = torch.empty(E.enkf_workspace_bytes(n, m, N), dtype=torch.uint8, device="cuda")
+
+                def bank():
+                    E.enkf_bank_predict(desc, B, w1, sig, x, P, F=dF, factor=AQ, status=st)
+                    E.enkf_bank_update(desc, B, dR, z, w2, sig, x, P, H=dH, factor=AR, S=S, SI=SI, K=K, status=st)
+
+                def loop_launches():
+                    for b in range(B):
+                        E.enkf_predict(desc, w1[b], sig[b], x[b], P[b], ws, F=dF, factor=AQ, status=st[b:b + 1])
+                        E.enkf_update(desc, dR, z[b], w2[b], sig[b], x[b], P[b], ws, H=dH, factor=AR, S=S[b], SI=SI[b], K=K[b],
+                                      status=st[b:b + 1])
+
+                def redraw():
+                    w1.normal_()
+                    w2.normal_()
+                bank()                                                  # warm-up
+                torch.cuda.synchronize()
+                assert int(st.abs().max()) == 0
+                ms = _events(bank, a.reps, redraw)
+                assert int(st.abs().max()) == 0 and bool(torch.isfinite(x).all())
+                loop_launches()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                lms = _events(loop_launches, 1 if B >= 10000 else 3, redraw)
+                launch_wall = (time.perf_counter() - t0) / len(lms)
+                assert int(st.abs().max()) == 0
+                # the class loop: B objects, as a user of the parent commit writes it
+                gen = torch.Generator(device="cuda").manual_seed(1)
+                fs = [EnsembleKalmanFilter(x=np.zeros(n), P=np.eye(n), dim_z=m, dt=1., N=N, hx=H, fx=F, noise="device", generator=gen)
+                      for _ in range(B)]
+                for f in fs:
+                    f.Q, f.R = Q, R
+                zs = np.zeros(m)
+                walls = []
+                for rep in range(1 + (1 if B >= 10000 else a.loop_reps)):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for f in fs:
+                        f.predict()
+                        f.update(zs)
+                    torch.cuda.synchronize()
+                    walls.append(time.perf_counter() - t0)
+                del fs
+                med = float(np.median(ms))
+                per_n = (3 * n + (2 * n + m)) if N <= 64 else (3 * n + (3 * n + m))
+                alg = 8.0 * B * N * per_n
+                row = dict(bank=True, shape=[n, m], layout=layout, tracks=B, members=N, route="wave" if N <= 64 else "workgroup",
+                           bank_ms_median=round(med, 4), bank_ms_min=round(min(ms), 4), launches_timed=a.reps,
+                           algorithmic_bytes_per_cycle=alg, hbm_fraction_8TBs=alg / (med * 1e-3) / 8e12,
+                           loop_launches_ms_median=round(float(np.median(lms)), 3), loop_launches_wall_ms=round(launch_wall * 1e3, 3),
+                           loop_class_wall_ms=round(float(np.median(walls[1:])) * 1e3, 3), loop_class_reps=len(walls) - 1,
+                           speedup_vs_loop_launches=round(float(np.median(lms)) / med, 1),
+                           speedup_vs_class_loop_wall=round(float(np.median(walls[1:])) * 1e3 / med, 1))
+                print(json.dumps(row), flush=True)
+                rows.append(row)
+                del sig, w1, w2
+                torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--members", type=int, nargs="+", default=[1 << 20, 1 << 23])
+    ap.add_argument("--bank", action="store_true")
+    ap.add_argument("--tracks", type=int, nargs="+", default=[100, 1000, 10000])
+    ap.add_argument("--sizes", type=int, nargs="+", default=[32, 64, 256, 1024])
+    ap.add_argument("--loop-reps", type=int, default=2)
     ap.add_argument("--out")
     a = ap.parse_args()
+    if a.bank:
+        rows = bank_rows(a)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(dict(when=time.strftime("%Y-%m-%d"), rows=rows), f, indent=1)
+        return
     import torch
     from filterpy_amd import _engine as E
     from filterpy_amd.kalman.ensemble_kalman_filter import _factor
