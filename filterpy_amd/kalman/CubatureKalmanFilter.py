@@ -48,13 +48,9 @@ import numpy as np
 from .. import _engine as E
 from ..common.helpers import logpdf
 from ._bank import _desc
+from ._callable import _CallableHost, alloc_histories, as_records, host_histories, status, to_rec
 
 __all__ = ["CubatureKalmanFilter", "spherical_radial_sigmas", "ckf_transform"]
-
-
-def _status(N, like):
-    import torch
-    return torch.zeros(N, dtype=torch.int32, device=like.device)
 
 
 def spherical_radial_sigmas(x, P):
@@ -66,7 +62,7 @@ def spherical_radial_sigmas(x, P):
     N = Pb.shape[0]
     xb = np.broadcast_to(np.asarray(x, dtype=np.float64).reshape(-1, n), (N, n))
     dx, dP = E.to_records(xb, "aos", 0), E.to_records(Pb, "aos", 0)
-    sig, st = E.alloc_records((), N, 2 * n * n, "aos"), _status(N, dx)
+    sig, st = E.alloc_records((), N, 2 * n * n, "aos"), status(N, dx)
     E.ckf_sigma_points(n, N, "aos", dx, dP, sig, st)
     E.raise_on_status(st, "spherical_radial_sigmas")
     out = E.from_records(sig, "aos", 0, (2 * n, n))
@@ -88,20 +84,12 @@ def ckf_transform(Xs, Q):
     return (x, P) if bank else (x[0].reshape(d, 1), P[0])
 
 
-class CubatureKalmanFilter(object):
+class CubatureKalmanFilter(_CallableHost):
     """filterpy.kalman.CubatureKalmanFilter (CubatureKalmanFilter.py:101-445) on the GPU: same attributes, defaults and results."""
 
     def __init__(self, dim_x, dim_z, dt, hx, fx, x_mean_fn=None, z_mean_fn=None, residual_x=None, residual_z=None,
                  n_tracks=None, vectorized=False, layout="soa", device_callables=False):
-        if device_callables and n_tracks is None:
-            raise ValueError("device_callables=True needs a bank: pass n_tracks=N (use N = 1 for one filter)")
-        if dim_x < 1 or dim_z < 1:
-            raise ValueError("dim_x and dim_z must be 1 or greater")
-        if layout not in E.LAYOUTS:
-            raise ValueError(f"layout must be one of {sorted(E.LAYOUTS)}")
-        self._N = n_tracks
-        self._layout = layout
-        self._mode = "torch" if device_callables else ("vec" if vectorized else "loop")
+        self._preamble(n_tracks, vectorized, device_callables, layout, dims=(dim_x, dim_z))
         lead = () if n_tracks is None else (n_tracks,)
         self.Q = np.eye(dim_x)
         self.R = np.eye(dim_z)
@@ -139,27 +127,6 @@ class CubatureKalmanFilter(object):
         """fx and hx were handed over as matrices"""
         return (not callable(self.fx)) and (not callable(self.hx))
 
-    def _unb(self, a):
-        return a if self._N is not None else a[0]
-
-    def _xb(self):
-        """x as (N, n); a single filter's x is (n,) or (n, 1)"""
-        n, N = self.dim_x, self._N or 1
-        x = np.asarray(self.x, dtype=np.float64)
-        ok = x.shape == (N, n) if self._N is not None else x.shape in ((n,), (n, 1))
-        if not ok:
-            raise ValueError(f"x has shape {x.shape}, expected " + (f"({N}, {n})" if self._N is not None else f"({n},) or ({n}, 1)"))
-        return np.ascontiguousarray(x.reshape(N, n))
-
-    def _Pb(self):
-        n, N = self.dim_x, self._N or 1
-        P = np.asarray(self.P, dtype=np.float64)
-        if P.shape == (n, n):
-            P = np.broadcast_to(P, (N, n, n))
-        if P.shape != (N, n, n):
-            raise ValueError(f"P has shape {P.shape}, expected ({N}, {n}, {n})" + (f" or ({n}, {n})" if self._N else ""))
-        return np.ascontiguousarray(P)
-
     def _noise(self, A, k, name):
         M = np.asarray(A, dtype=np.float64)
         if M.ndim == 0:
@@ -194,29 +161,15 @@ class CubatureKalmanFilter(object):
             raise ValueError(f"{name} has shape {A.shape}, expected ({r}, {c})")
         return np.ascontiguousarray(A)
 
-    def _rec_view(self, rec, k, d):
-        """device records of N (k x d) blocks -> torch view (N, k, d), no copy"""
-        N = self._N or 1
-        if self._layout == "aos":
-            return rec.view(N, k, d)
-        return rec.view(k, d, N).permute(2, 0, 1)
-
     def _to_rec(self, t, k, d):
         """(N, k, d) as a callable returned it (torch tensor or array) -> device records in the bank's layout"""
-        import torch
-        N = self._N or 1
-        if self._mode == "torch":
-            if (not isinstance(t, torch.Tensor) or t.device.type != E.require_gpu().type or t.dtype != torch.float64
-                    or tuple(t.shape) != (N, k, d)):
-                raise TypeError(f"device callables must return a float64 CUDA tensor shaped {(N, k, d)}")
-        else:
-            a = np.asarray(t, dtype=np.float64)
-            if a.shape != (N, k, d):
-                raise ValueError(f"the callable returned shape {a.shape}, expected {(N, k, d)}")
-            t = E.dev(a)
-        if self._layout == "aos":
-            return t.contiguous().view(N, k * d)
-        return t.permute(1, 2, 0).contiguous().view(k * d, N)
+        return to_rec(t, self._N or 1, (k, d), self._layout, self._mode == "torch")
+
+    def _by_products(self):
+        """records for the y, K, S and SI of one update"""
+        n, m, N, lay = self.dim_x, self.dim_z, self._N or 1, self._layout
+        return dict(y=E.alloc_records((), N, m, lay), K=E.alloc_records((), N, n * m, lay), S=E.alloc_records((), N, m * m, lay),
+                    SI=E.alloc_records((), N, m * m, lay))
 
     def _user(self, fn, sig, d_out, *args):
         """fx / hx on the points sig, a (N, k, d) device view, in the mode's calling convention -> records (N, k, d_out)"""
@@ -224,8 +177,7 @@ class CubatureKalmanFilter(object):
         if not callable(fn):                                   # a matrix next to a callable: one kernel (fk_ut_linear_map_f64)
             M = self._matrix(fn, d_out, d_in, "the model matrix")
             out = E.alloc_records((), N, k * d_out, self._layout)
-            src = sig.contiguous().view(N, k * d_in) if self._layout == "aos" else sig.permute(1, 2, 0).contiguous().view(k * d_in, N)
-            E.ut_linear_map(d_in, d_out, k, N, self._layout, E.dev(M), src, out)
+            E.ut_linear_map(d_in, d_out, k, N, self._layout, E.dev(M), as_records(sig, N, self._layout), out)
             return out
         if self._mode == "torch":
             return self._to_rec(fn(sig, *args), k, d_out)
@@ -331,7 +283,7 @@ class CubatureKalmanFilter(object):
         n, N, lay = self.dim_x, self._N or 1, self._layout
         dQ = E.dev(self._noise(self.Q, n, "Q"))
         dx, dP = E.to_records(self._xb(), lay, 0).clone(), E.to_records(self._Pb(), lay, 0).clone()
-        st = _status(N, dx)
+        st = status(N, dx)
         if self._linear:
             F = self._matrix(self.fx, n, n, "fx")
             pts = E.alloc_records((), N, n + n * n, lay)
@@ -367,11 +319,10 @@ class CubatureKalmanFilter(object):
                              "make x an (n, 1) column (predict() does)")
         dx, dP = E.to_records(xb, lay, 0).clone(), E.to_records(self._Pb(), lay, 0).clone()
         dz, dR = E.to_records(zb, lay, 0), E.dev(Rm)
-        st = _status(N, dx)
-        by = dict(y=E.alloc_records((), N, m, lay), K=E.alloc_records((), N, n * m, lay), S=E.alloc_records((), N, m * m, lay),
-                  SI=E.alloc_records((), N, m * m, lay))
+        st = status(N, dx)
+        by = self._by_products()
         if self._linear:
-            H = self._matrix(self.hx, m, n, "hx")
+            H =self._matrix(self.hx, m, n, "hx")
             pts = E.to_records(self._points_records(), lay, 0)
             E.ckf_linear_update(_desc(n, m, 0, N, 1, lay), E.dev(H), dR, dz, dx, dP, pts, status=st, **by)
             self._sh = None
@@ -417,9 +368,8 @@ class CubatureKalmanFilter(object):
         dQ = E.dev(self._noise(self.Q, n, "Q"))
         dx, dP = E.to_records(self._xb(), lay, 0).clone(), E.to_records(self._Pb(), lay, 0).clone()
         dzs = E.to_records(zarr, lay, 1)
-        st = _status(N, dx)
-        outs = [E.alloc_records((T,), N, n, lay), E.alloc_records((T,), N, n * n, lay),
-                E.alloc_records((T,), N, n, lay), E.alloc_records((T,), N, n * n, lay)]
+        st = status(N, dx)
+        outs = alloc_histories(T, N, n, lay)
         fused = self._linear and Rs is None and saver is None
         if fused:
             F, H = self._matrix(self.fx, n, n, "fx"), self._matrix(self.hx, m, n, "hx")
@@ -444,17 +394,14 @@ class CubatureKalmanFilter(object):
         else:
             sf, last = None, None
             last_upd = max([t for t in range(T) if present[t]], default=-1)
-            stt = _status(N, dx)                              # each kernel writes its own status: OR them over the steps
+            stt = status(N, dx)                              # each kernel writes its own status: OR them over the steps
             for t in range(T):
                 sf = self._dev_predict(dx, dP, dQ, self._dt, stt, ())
                 st.bitwise_or_(stt)
                 outs[2][t].copy_(dx.reshape(outs[2][t].shape))
                 outs[3][t].copy_(dP.reshape(outs[3][t].shape))
                 if present[t]:
-                    by = None
-                    if t == last_upd:                         # the by-products the step loop would leave on the object
-                        by = dict(y=E.alloc_records((), N, m, lay), K=E.alloc_records((), N, n * m, lay),
-                                  S=E.alloc_records((), N, m * m, lay), SI=E.alloc_records((), N, m * m, lay))
+                    by = self._by_products() if t == last_upd else None   # (what the step loop would leave on the object)
                     sh = self._dev_update(dx, dP, sf, dzs[t], E.dev(self._R(None if Rs is None else Rs[t])), stt, (), by)
                     st.bitwise_or_(stt)
                     if by is not None:
@@ -483,8 +430,8 @@ class CubatureKalmanFilter(object):
             self.z = deepcopy(zs[T - 1]) if present[T - 1] else np.array([[None] * m]).T
         if device_outputs:
             return tuple(outs)
-        res = [E.from_records(o, lay, 1, s) for o, s in zip(outs, ((n,), (n, n), (n,), (n, n)))]
-        return tuple(res) if self._N is not None else tuple(r[:, 0] for r in res)
+        res = host_histories(outs, n, lay)
+        return res if self._N is not None else tuple(r[:, 0] for r in res)
 
     # ------------------------------------------------------------------------------------------------- the lazy scalars --
     @property

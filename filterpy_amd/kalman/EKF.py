@@ -63,34 +63,20 @@ import numpy as np
 from .. import _engine as E
 from .._abi import FK_KF_FLAG_R_JOSEPH_DIAG, FK_MODEL_PER_TRACK, FK_MODEL_SHARED
 from ._bank import _step_control
+from ._callable import _CallableHost, alloc_histories, as_records, host_histories, status, to_rec, track_rows
 
 __all__ = ["ExtendedKalmanFilter"]
-
-
-def _status(N, like):
-    import torch
-    return torch.zeros(N, dtype=torch.int32, device=like.device)
 
 
 def _tuple(a):
     return a if isinstance(a, tuple) else (a,)
 
 
-class ExtendedKalmanFilter(object):
+class ExtendedKalmanFilter(_CallableHost):
     """filterpy.kalman.ExtendedKalmanFilter (EKF.py:32-428) on the GPU: same attributes, defaults and results."""
 
     def __init__(self, dim_x, dim_z, dim_u=0, n_tracks=None, vectorized=False, layout="soa", device_callables=False):
-        if device_callables and n_tracks is None:
-            raise ValueError("device_callables=True needs a bank: pass n_tracks=N (use N = 1 for one filter)")
-        if vectorized and n_tracks is None:
-            raise ValueError("vectorized=True needs a bank: pass n_tracks=N")
-        if dim_x < 1 or dim_z < 1:
-            raise ValueError("dim_x and dim_z must be 1 or greater")
-        if layout not in E.LAYOUTS:
-            raise ValueError(f"layout must be one of {sorted(E.LAYOUTS)}")
-        self._N = n_tracks
-        self._layout = layout
-        self._mode = "torch" if device_callables else ("vec" if vectorized else "loop")
+        self._preamble(n_tracks, vectorized, device_callables, layout, dims=(dim_x, dim_z), vectorized_bank_only=True)
         self._resident = None                   # batch_filter's fused loop: the model's device operands, uploaded once
         self.dim_x = dim_x
         self.dim_z = dim_z
@@ -118,24 +104,6 @@ class ExtendedKalmanFilter(object):
         self.P_post = self.P.copy()
 
     # ---------------------------------------------------------------------------------------------------------- helpers --
-    def _xb(self):
-        """x as (N, n); a single filter's x is (n,) or (n, 1)"""
-        n, N = self.dim_x, self._N or 1
-        x = np.asarray(self.x, dtype=np.float64)
-        ok = x.shape == (N, n) if self._N is not None else x.shape in ((n,), (n, 1))
-        if not ok:
-            raise ValueError(f"x has shape {x.shape}, expected " + (f"({N}, {n})" if self._N is not None else f"({n},) or ({n}, 1)"))
-        return np.ascontiguousarray(x.reshape(N, n))
-
-    def _Pb(self):
-        n, N = self.dim_x, self._N or 1
-        P = np.asarray(self.P, dtype=np.float64)
-        if P.shape == (n, n):
-            P = np.broadcast_to(P, (N, n, n))
-        if P.shape != (N, n, n):
-            raise ValueError(f"P has shape {P.shape}, expected ({N}, {n}, {n})" + (f" or ({n}, {n})" if self._N else ""))
-        return np.ascontiguousarray(P)
-
     def _matrix(self, A, r, c, name):
         """a model matrix: (r, c), or for a bank (N, r, c)"""
         M = np.asarray(A, dtype=np.float64)
@@ -207,22 +175,11 @@ class ExtendedKalmanFilter(object):
 
     def _to_rec(self, t, shape, what):
         """(N,) + shape as a callable returned it (array or, with device callables, tensor) -> device records"""
-        import torch
-        N = self._N or 1
-        if self._mode == "torch":
-            if (not isinstance(t, torch.Tensor) or t.device.type != E.require_gpu().type or t.dtype != torch.float64
-                    or tuple(t.shape) != (N,) + shape):
-                raise TypeError(f"device callables: {what} must return a float64 CUDA tensor shaped {(N,) + shape}")
-            t = t.reshape(N, -1)
-            return t.contiguous() if self._layout == "aos" else t.t().contiguous()
-        a = np.asarray(t, dtype=np.float64)
-        if a.shape != (N,) + shape:
-            raise ValueError(f"{what} returned shape {a.shape}, expected {(N,) + shape}")
-        return E.to_records(np.ascontiguousarray(a), self._layout, 0)
+        return to_rec(t, self._N or 1, shape, self._layout, self._mode == "torch", what)
 
     def _xview(self, dx):
         """x records -> (N, n) device tensor for the device callables"""
-        return dx if self._layout == "aos" else dx.t().contiguous()
+        return track_rows(dx, self._layout)
 
     def _jacobian(self, HJacobian, args, xb, dx=None):
         """H of every track -> device records [N][m*n]"""
@@ -299,14 +256,13 @@ class ExtendedKalmanFilter(object):
     def _to_urec(self, uv):
         import torch
         if isinstance(uv, torch.Tensor):
-            t = uv.to(dtype=torch.float64)
-            return t.contiguous() if self._layout == "aos" else t.t().contiguous()
+            return as_records(uv.to(dtype=torch.float64), self._N or 1, self._layout)
         return E.to_records(uv, self._layout, 0)
 
     def _predict(self, u, keep_x):
         N, lay = self._N or 1, self._layout
         dx, dP = E.to_records(self._xb(), lay, 0).clone(), E.to_records(self._Pb(), lay, 0).clone()
-        st = _status(N, dx)
+        st = status(N, dx)
         self._dev_predict(dx, dP, u, st)
         E.raise_on_status(st, "ExtendedKalmanFilter.predict")
         x_own = self.x
@@ -409,7 +365,7 @@ class ExtendedKalmanFilter(object):
         mk, dmask = self._mask(mask, dx)
         dH = self._jacobian(HJacobian, args, xb, dx)
         y, dy = self._innovation(z, Hx, hx_args, residual, xb, dx)
-        st = _status(N, dx)
+        st = status(N, dx)
         by = self._by_products(dx, mk is not None)
         self._dev_update(dx, dP, dH, dy, Rm, flags, st, mask=dmask, by=by)
         E.raise_on_status(st, "ExtendedKalmanFilter.update (S is singular)")
@@ -433,7 +389,7 @@ class ExtendedKalmanFilter(object):
         dx, dP = E.to_records(xb, lay, 0).clone(), E.to_records(self._Pb(), lay, 0).clone()
         dH = self._jacobian(HJacobian, args, xb, dx)           # at the state before the predict (:222)
         x_pre, P_pre = np.copy(self.x), np.copy(self.P)
-        st = _status(N, dx)
+        st = status(N, dx)
         self._dev_predict(dx, dP, u, st)
         E.raise_on_status(st, "ExtendedKalmanFilter.predict_update")
         xp = E.from_records(dx, lay, 0, (self.dim_x,))
@@ -481,11 +437,10 @@ class ExtendedKalmanFilter(object):
             return tuple(outs)
         dx, dP = E.to_records(self._xb(), lay, 0).clone(), E.to_records(self._Pb(), lay, 0).clone()
         dzs = zs if isinstance(zs, torch.Tensor) else E.dev(np.asarray(zs, dtype=np.float64))
-        outs = [E.alloc_records((T,), N, n, lay), E.alloc_records((T,), N, n * n, lay),
-                E.alloc_records((T,), N, n, lay), E.alloc_records((T,), N, n * n, lay)]
+        outs = alloc_histories(T, N, n, lay)
         if T:
             Rm, flags = self._R(None)
-            st, stt = _status(N, dx), _status(N, dx)
+            st, stt = status(N, dx), status(N, dx)
             # F, Q, R, B go up once (the attributes as they stand now hold for all T steps), and so does a (T, N, dim_u) array
             # of controls.  Per step the loop then adds to the launches only the callables and ONE device copy of x and P into
             # the prior histories: the kernels work on x and P in place, so the prior a step leaves is copied out before the
@@ -508,7 +463,7 @@ class ExtendedKalmanFilter(object):
             self.z = zl.cpu().numpy() if isinstance(zl, torch.Tensor) else deepcopy(zl)
         if device_outputs:
             return tuple(outs)
-        return tuple(E.from_records(o, lay, 1, s) for o, s in zip(outs, ((n,), (n, n), (n,), (n, n))))
+        return host_histories(outs, n, lay)
 
     def _fused_steps(self, T, dx, dP, dzs, outs, u_at, Rm, flags, st, stt, HJacobian, Hx, args, hx_args, residual):
         """one fk_ekf_predict_f64, T - 1 fk_ekf_step_f64, one fk_ekf_update_f64 on resident records -> the last update's

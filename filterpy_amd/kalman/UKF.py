@@ -44,21 +44,19 @@ import numpy as np
 
 from .. import _engine as E
 from ..common.helpers import logpdf
+from ._callable import _CallableHost, status, to_rec
 
 __all__ = ["UnscentedKalmanFilter"]
 
 
-class UnscentedKalmanFilter(object):
+class UnscentedKalmanFilter(_CallableHost):
     def __init__(self, dim_x, dim_z, dt, hx, fx, points, sqrt_fn=None, x_mean_fn=None, z_mean_fn=None,
                  residual_x=None, residual_z=None, state_add=None, n_tracks=None, vectorized=False,
                  layout="soa", device_callables=False):
-        if device_callables and n_tracks is None:
-            raise ValueError("device_callables=True needs a bank: pass n_tracks=N (use N = 1 for one filter)")
+        self._preamble(n_tracks, vectorized, device_callables, layout)      # (neither the dims nor the layout are checked here)
         self._dim_x, self._dim_z = dim_x, dim_z
-        self._N = n_tracks
         self._devcall = bool(device_callables)
         self._vec = vectorized or n_tracks is not None and not callable(fx)
-        self._layout = layout
         shape = (dim_x,) if n_tracks is None else (n_tracks, dim_x)
         self.x = np.zeros(shape)
         self.P = np.eye(dim_x) if n_tracks is None else np.tile(np.eye(dim_x), (n_tracks, 1, 1))
@@ -69,7 +67,6 @@ class UnscentedKalmanFilter(object):
         self._num_sigmas = points.num_sigmas()
         self.hx, self.fx = hx, fx
         self.x_mean, self.z_mean = x_mean_fn, z_mean_fn
-        self._mode = "torch" if device_callables else ("vec" if vectorized else "loop")
         self._ut_fn = None
         self._log_likelihood = log(sys.float_info.min)
         self._likelihood = sys.float_info.min
@@ -108,9 +105,6 @@ class UnscentedKalmanFilter(object):
         out = [[fn(s, *args, **kw) for s in trk] for trk in sig]
         return np.asarray(out, dtype=np.float64).reshape(sig.shape[0], sig.shape[1], -1)
 
-    def _unb(self, a):
-        return a if self._N is not None else a[0]
-
     # ------------------------------------------------- device-resident split path --
     @property
     def _hooked(self):
@@ -145,26 +139,13 @@ class UnscentedKalmanFilter(object):
                 self._ut_fn = old
         return cm()
 
-    def _rec_view(self, rec, k, d):
-        """device records of N (k x d) blocks -> torch view (N, k, d), no copy"""
-        N = self._N or 1
-        if self._layout == "aos":
-            return rec.view(N, k, d)
-        return rec.view(k, d, N).permute(2, 0, 1)
-
     def _vec_view(self, rec, d):
         return self._rec_view(rec, 1, d)[:, 0, :]
 
     def _to_rec(self, t, k, d):
-        """torch tensor (N, k, d) as the callable returned it -> device records in the bank's layout"""
-        import torch
-        N = self._N or 1
-        if (not isinstance(t, torch.Tensor) or t.device.type != E.require_gpu().type or t.dtype != torch.float64
-                or tuple(t.shape) != (N, k, d)):
-            raise TypeError(f"device callables must return a float64 CUDA tensor shaped {(N, k, d)}")
-        if self._layout == "aos":
-            return t.contiguous().view(N, k * d)
-        return t.permute(1, 2, 0).contiguous().view(k * d, N)
+        """torch tensor (N, k, d) as the callable returned it -> device records in the bank's layout (a tensor in every mode: the
+        host modes' results come back through _tt)"""
+        return to_rec(t, self._N or 1, (k, d), self._layout, True)
 
     @staticmethod
     def _tt(a, like):
@@ -344,10 +325,9 @@ class UnscentedKalmanFilter(object):
 
     def _res_predict(self, dt, fx, **fx_args):
         """predict() with state resident for the step (device callables and / or hooks)"""
-        import torch
         n, k, N, lay = self._dim_x, self._num_sigmas, self._N or 1, self._layout
         dx, dP = E.to_records(self._b(self.x, (n,)), lay, 0), E.to_records(self._b(self.P, (n, n)), lay, 0)
-        st = torch.zeros(N, dtype=torch.int32, device=dx.device)
+        st = status(N, dx)
         self._sig_dev = self._dev_predict(dx, dP, self._dev_consts(), dt, st, fx, **fx_args)
         E.raise_on_status(st, "UnscentedKalmanFilter.predict")
         self.x, self.P = self._unb(E.from_records(dx, lay, 0, (n,))), self._unb(E.from_records(dP, lay, 0, (n, n)))
@@ -355,13 +335,12 @@ class UnscentedKalmanFilter(object):
         self.x_prior, self.P_prior = np.copy(self.x), np.copy(self.P)
 
     def _res_update(self, z, R, hx, **hx_args):
-        import torch
         n, m, k, N, lay = self._dim_x, self._dim_z, self._num_sigmas, self._N or 1, self._layout
         dx, dP = E.to_records(self._b(self.x, (n,)), lay, 0), E.to_records(self._b(self.P, (n, n)), lay, 0)
         sig = E.to_records(np.asarray(self.sigmas_f, dtype=np.float64).reshape(N, k, n), lay, 0)
         zb = np.asarray(z, dtype=np.float64).reshape(N, m)
         dz, dK = E.to_records(zb, lay, 0), E.alloc_records((), N, n * m, lay)
-        st = torch.zeros(N, dtype=torch.int32, device=dx.device)
+        st = status(N, dx)
         c = self._dev_consts()
         Rd = None if R is None else E.dev(np.eye(m) * R if np.isscalar(R) else np.broadcast_to(np.asarray(R, dtype=np.float64), (m, m)).copy())
         sh, zp, S = self._dev_update(dx, dP, sig, dz, c, st, dK=dK, hx=hx, R=Rd, **hx_args)
@@ -392,7 +371,7 @@ class UnscentedKalmanFilter(object):
                     zarr[i] = np.asarray(z, dtype=np.float64).reshape(N, m)
             dzs = E.to_records(zarr, lay, 1)
         means, covs = E.alloc_records((T,), N, n, lay), E.alloc_records((T,), N, n * n, lay)
-        st = torch.zeros(N, dtype=torch.int32, device=dx.device)
+        st = status(N, dx)
         k = self._num_sigmas
         last_upd = max([t for t in range(T) if present[t]], default=-1)
         last = prior = None
@@ -447,10 +426,9 @@ class UnscentedKalmanFilter(object):
         fx = self.fx if fx is None else fx
         n = self._dim_x
         if self._resident:
-            import torch
             k, N, lay = self._num_sigmas, self._N or 1, self._layout
             dx, dP = E.to_records(self._b(self.x, (n,)), lay, 0), E.to_records(self._b(self.P, (n, n)), lay, 0)
-            st = torch.zeros(N, dtype=torch.int32, device=dx.device)
+            st = status(N, dx)
             sig = E.alloc_records((), N, k * n, lay)
             self._dev_sigmas(dx, dP, sig, st)
             E.raise_on_status(st, "UnscentedKalmanFilter.compute_process_sigmas")
@@ -480,7 +458,6 @@ class UnscentedKalmanFilter(object):
     # ----------------------------------------------------------------- update --
     def update(self, z, R=None, UT=None, hx=None, **hx_args):
         """UKF.py:413-491."""
-        import torch
         from .unscented_transform import unscented_transform
         if z is None:
             self.z = np.array([[None] * self._dim_z]).T
@@ -515,7 +492,7 @@ class UnscentedKalmanFilter(object):
         E.ut_cross_variance(n, m, k, N, lay, dx, dzp, E.to_records(sf, lay, 0), E.to_records(sh, lay, 0),
                             E.dev(np.asarray(self.Wc, dtype=np.float64)), dPxz)
         dK = E.alloc_records((), N, n * m, lay)
-        st = torch.zeros(N, dtype=torch.int32, device=dx.device)
+        st = status(N, dx)
         E.ukf_correct(n, m, N, lay, dPxz, dzp, dS, dz, dx, dP, dK, st)
         E.raise_on_status(st, "UnscentedKalmanFilter.update")
         self.S = self._unb(S)
@@ -588,7 +565,7 @@ class UnscentedKalmanFilter(object):
             x_init, P_init = np.array(self.x, dtype=np.float64), np.array(self.P, dtype=np.float64)
             dx, dP = E.to_records(self._b(self.x, (n,)), lay, 0), E.to_records(self._b(self.P, (n, n)), lay, 0)
             means, covs = E.alloc_records((T,), N, n, lay), E.alloc_records((T,), N, n * n, lay)
-            st = torch.zeros(N, dtype=torch.int32, device=dx.device)
+            st = status(N, dx)
             dm = None if mask.all() else torch.as_tensor(mask, device=dx.device)
             E.ukf_linear_batch(n, m, N, T, lay, self.points_fn.scale, E.dev(self.fx), E.dev(self.hx),
                                E.dev(np.broadcast_to(self.Q, (n, n)).copy()), E.dev(np.broadcast_to(self.R, (m, m)).copy()),
@@ -653,7 +630,7 @@ class UnscentedKalmanFilter(object):
         Ks = torch.zeros_like(ps)
         sig = E.alloc_records((), N, k * n, lay)
         xb, Pb, Pxb = E.alloc_records((), N, n, lay), E.alloc_records((), N, n * n, lay), E.alloc_records((), N, n * n, lay)
-        st = torch.zeros(N, dtype=torch.int32, device=xs.device)
+        st = status(N, xs)
         rx = self.residual_x
         for j in reversed(range(T - 1)):
             self._dev_sigmas(xs[j], ps[j], sig, st)
@@ -703,7 +680,7 @@ class UnscentedKalmanFilter(object):
             dX = E.to_records(Xa.reshape(T, N, n), lay, 1)
             dP = E.to_records(np.asarray(Ps, dtype=np.float64).reshape(T, N, n, n), lay, 1)
             oxs, ops, oK = E.alloc_records((T,), N, n, lay), E.alloc_records((T,), N, n * n, lay), E.alloc_records((T,), N, n * n, lay)
-            st = torch.zeros(N, dtype=torch.int32, device=dX.device)
+            st = status(N, dX)
             E.ukf_linear_rts(n, N, T, lay, self.points_fn.scale, E.dev(np.asarray(self.fx, dtype=np.float64)),
                              E.dev(np.broadcast_to(np.asarray(self.Q, dtype=np.float64), (n, n)).copy()),
                              E.dev(np.asarray(self.Wm, dtype=np.float64)), E.dev(np.asarray(self.Wc, dtype=np.float64)),
@@ -736,7 +713,7 @@ class UnscentedKalmanFilter(object):
                                 E.to_records(sf, lay, 0), dWc, dPxb)
             dx, dP = E.to_records(xs[j], lay, 0), E.to_records(ps[j], lay, 0)
             dK = E.alloc_records((), N, n * n, lay)
-            st = torch.zeros(N, dtype=torch.int32, device=dx.device)
+            st = status(N, dx)
             E.ukf_rts_correct(n, N, lay, dPxb, dxb, dPb, E.to_records(xs[j + 1], lay, 0),
                               E.to_records(ps[j + 1], lay, 0), dx, dP, dK, st)
             E.raise_on_status(st, "UnscentedKalmanFilter.rts_smoother")

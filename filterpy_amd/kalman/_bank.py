@@ -1,10 +1,12 @@
 """What the filters whose kernels take ONE model for every track share on the host (square_root.py, information_filter.py,
 fixed_lag_smoother.py): the descriptor, the control-input rules, the shape checks of the single-filter classes and the
-plumbing of the banks.  Private: the three modules import from here and not from each other."""
+plumbing of the banks.  Private: the three modules import from here and not from each other.  The filters that run the
+caller's callables between the kernels share _callable.py instead; the status word and the four histories come from there."""
 import numpy as np
 
 from .. import _engine as E
 from .._abi import FK_MODEL_SHARED
+from ._callable import alloc_histories, status
 
 
 def _desc(n, m, nu, N, T, layout, update_first=False, flags=0):
@@ -194,12 +196,11 @@ class _SharedModelBank(object):
     # -- steps --------------------------------------------------------------------------------------------------------------
     def predict(self, u=None):
         """one predict for every track: u (n_tracks, dim_u) or None"""
-        import torch
         n, N = self.dim_x, self.n_tracks
         F, Q, _, _ = self._model()
         B, du = self._controls(None if u is None else np.asarray(u, dtype=np.float64).reshape(1, N, -1), 1)
         x, C = self._state()
-        st = torch.zeros(N, dtype=torch.int32, device=x.device)
+        st = status(N, x)
         nu = 0 if B is None else int(B.shape[1])
         self._engine("predict")(_desc(n, self.dim_z, nu, N, 1, self.layout), F, Q, x, C, B=B,
                                 u=None if du is None else du.reshape(du.shape[1:]), status=st)
@@ -208,7 +209,6 @@ class _SharedModelBank(object):
 
     def _update(self, z, R, mask):
         """one update for every track; R: what replaces the model's fourth matrix for this call (`_model(R)`), or None"""
-        import torch
         n, m, N = self.dim_x, self.dim_z, self.n_tracks
         _, _, H, Rm = self._model(R)
         dz, dm = self._measurements(np.asarray(z, dtype=np.float64).reshape(1, N, m), 1,
@@ -216,7 +216,7 @@ class _SharedModelBank(object):
         x, C = self._state()
         outs = {kw: E.to_records(np.asarray(getattr(self, attr), dtype=np.float64).reshape(N, -1), self.layout, 0).clone()
                 for attr, kw, _ in self._BYPRODUCTS}
-        st = torch.zeros(N, dtype=torch.int32, device=x.device)
+        st = status(N, x)
         self._engine("update")(_desc(n, m, 0, N, 1, self.layout), H, Rm, dz.reshape(dz.shape[1:]), x, C,
                                mask=None if dm is None else dm.reshape(N), status=st, **outs)
         self._raise_on_status(st, "update")
@@ -228,7 +228,6 @@ class _SharedModelBank(object):
         """(means, covs, means_p, covs_p) of the whole run in the subclass's form of the covariance, ONE launch; the state is
         left alone.  zs (T, N, dim_z) with NaN rows missing (or device records in `layout`), mask (T, N) bool (False =
         missing), us (T, N, dim_u)."""
-        import torch
         n, m, N = self.dim_x, self.dim_z, self.n_tracks
         T = int(zs.shape[0]) if hasattr(zs, "shape") else len(zs)
         if T == 0:
@@ -238,10 +237,8 @@ class _SharedModelBank(object):
         dz, dm = self._measurements(zs, T, mask)
         B, du = self._controls(us, T)
         x, C = self._state()
-        dev = x.device
-        means, means_p = E.alloc_records((T,), N, n, self.layout, dev), E.alloc_records((T,), N, n, self.layout, dev)
-        covs, covs_p = E.alloc_records((T,), N, n * n, self.layout, dev), E.alloc_records((T,), N, n * n, self.layout, dev)
-        st = torch.zeros(N, dtype=torch.int32, device=dev)
+        means, covs, means_p, covs_p = alloc_histories(T, N, n, self.layout, x.device)
+        st = status(N, x)
         nu = 0 if B is None else int(B.shape[1])
         self._engine("batch")(_desc(n, m, nu, N, T, self.layout, update_first), F, Q, H, R, dz, x, C, B=B, u=du, mask=dm,
                               means=means, covs=covs, means_p=means_p, covs_p=covs_p, status=st)

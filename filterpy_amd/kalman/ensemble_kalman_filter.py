@@ -55,6 +55,7 @@ import numpy as np
 
 from .. import _engine as E
 from ._bank import _desc
+from ._callable import status
 
 __all__ = ["EnsembleKalmanFilter", "EnsembleKalmanFilterBank"]
 
@@ -65,22 +66,27 @@ def _factor(cov):
     return np.ascontiguousarray(np.sqrt(s)[:, None] * v)
 
 
-class EnsembleKalmanFilter(object):
-    """filterpy.kalman.EnsembleKalmanFilter (ensemble_kalman_filter.py:36-309) on the GPU: same attributes and defaults."""
+class _Ensemble(object):
+    """What the one ensemble and the bank of them share.  `_lead` is () for EnsembleKalmanFilter and (n_tracks,) for the bank:
+    every array of the surface is _lead + the single filter's shape, and the device tensor has the members on its last two
+    axes.  A subclass states `_check_size`, `_given_x`, `_no_z`, `_draw`, `_apply`, `initialize`, `predict` and `update`."""
+    _REPR = ("dim_x", "dim_z", "dt", "N", "layout", "noise", "x", "P", "x_prior", "P_prior", "Q", "R", "K", "S", "sigmas", "hx",
+             "fx")
 
-    def __init__(self, x, P, dim_z, dt, N, hx, fx, *, noise="numpy", vectorized=False, device_callables=False, layout="soa",
-                 generator=None):
+    def __init__(self, lead, x, P, dim_z, dt, N, hx, fx, noise, vectorized, device_callables, layout, generator):
         if dim_z <= 0:
             raise ValueError('dim_z must be greater than zero')
         if N < 2:
             raise ValueError('N must be at least 2 (the covariances divide by N - 1)')
+        self._check_size(N, lead)
         if layout not in E.LAYOUTS:
             raise ValueError(f"layout must be one of {sorted(E.LAYOUTS)}")
         if not (noise in ("numpy", "device") or callable(noise)):
             raise ValueError('noise must be "numpy", "device" or a callable (mean, cov, N) -> (N, d)')
-        dim_x = len(x)
+        x, dim_x = self._given_x(x)
         if dim_x > 16 or dim_z > 8:
             raise NotImplementedError("dim_x/dim_z outside the compiled range (dim_x <= 16, dim_z <= 8)")
+        self._lead = lead
         self.dim_x = dim_x
         self.dim_z = dim_z
         self.dt = dt
@@ -92,11 +98,11 @@ class EnsembleKalmanFilter(object):
         self.device_callables = device_callables
         self.layout = layout
         self.generator = generator
-        self.K = np.zeros((dim_x, dim_z))
-        self.z = np.array([[None] * self.dim_z]).T
-        self.S = np.zeros((dim_z, dim_z))
-        self.SI = np.zeros((dim_z, dim_z))
-        self._sig = self._sig_host = self._ws = None
+        self.K = np.zeros(lead + (dim_x, dim_z))
+        self.z = self._no_z()
+        self.S = np.zeros(lead + (dim_z, dim_z))
+        self.SI = np.zeros(lead + (dim_z, dim_z))
+        self._sig = self._sig_host = None
 
         self.initialize(x, P)
         self.Q = np.eye(dim_x)
@@ -105,43 +111,95 @@ class EnsembleKalmanFilter(object):
         self._mean = np.zeros(dim_x)
         self._mean_z = np.zeros(dim_z)
 
+    def _check_size(self, N, lead):
+        """the subclass's own refusals, between those of N and of the layout"""
+
     # -- the ensemble ---------------------------------------------------------------------------------------------------------
     @property
     def sigmas(self):
-        """the ensemble as an (N, dim_x) NumPy array: downloaded on first read after a step, then cached"""
+        """the members as a _lead + (N, dim_x) NumPy array: downloaded on first read after a step, then cached"""
         if self._sig_host is None:
-            self._sig_host = E.from_records(self._sig, self.layout, 0, (self.dim_x,)).copy()
+            self._sig_host = E.from_records(self._sig, self.layout, len(self._lead), (self.dim_x,)).copy()
         return self._sig_host
 
     @sigmas.setter
     def sigmas(self, value):
         a = np.asarray(value, dtype=np.float64)
-        if a.shape != (self.N, self.dim_x):
-            raise ValueError(f"sigmas has shape {a.shape}, expected ({self.N}, {self.dim_x})")
-        self._sig = E.to_records(a, self.layout, 0)
+        if a.shape != self._lead + (self.N, self.dim_x):
+            raise ValueError(f"sigmas has shape {a.shape}, expected {self._lead + (self.N, self.dim_x)}")
+        self._sig = E.to_records(a, self.layout, len(self._lead))
         self._sig_host = None
 
     @property
     def sigmas_device(self):
-        """the ensemble's device tensor, in `layout`: (dim_x, N) for 'soa', (N, dim_x) for 'aos'"""
+        """the device tensor, in `layout`: _lead + (dim_x, N) for 'soa', _lead + (N, dim_x) for 'aos'"""
         return self._sig
 
     def _members(self):
-        """the device tensor as an (N, dim_x) view"""
-        return self._sig.t() if self.layout == "soa" else self._sig
+        """the device tensor as a _lead + (N, dim_x) view"""
+        return self._sig.transpose(-1, -2) if self.layout == "soa" else self._sig
 
     def _records(self, t, d):
-        """an (N, d) array or tensor -> device records in `layout`"""
+        """a _lead + (N, d) array or tensor -> device records in `layout`"""
         import torch
+        shape = self._lead + (self.N, d)
         if isinstance(t, torch.Tensor):
             t = E.dev(t)
-            if tuple(t.shape) != (self.N, d):
-                raise ValueError(f"expected an ({self.N}, {d}) tensor, got {tuple(t.shape)}")
-            return t.t().contiguous() if self.layout == "soa" else t
+            if tuple(t.shape) != shape:
+                raise ValueError(f"expected an {shape} tensor, got {tuple(t.shape)}")
+            return t.transpose(-1, -2).contiguous() if self.layout == "soa" else t
         a = np.asarray(t, dtype=np.float64)
-        if a.shape != (self.N, d):
-            raise ValueError(f"expected an ({self.N}, {d}) array, got {a.shape}")
-        return E.to_records(a, self.layout, 0)
+        if a.shape != shape:
+            raise ValueError(f"expected an {shape} array, got {a.shape}")
+        return E.to_records(a, self.layout, len(self._lead))
+
+    # -- the bookkeeping around a step --------------------------------------------------------------------------------------
+    def _check_inv(self):
+        if self.inv is not np.linalg.inv:
+            raise NotImplementedError(f"{type(self).__name__}.inv other than numpy.linalg.inv: the inverse is taken on the device")
+
+    def _given_R(self, R):
+        """update()'s R: None -> the attribute, a scalar -> eye * R (:250-254); the subclass checks the shape"""
+        if R is None:
+            R = self.R
+        if np.isscalar(R):
+            R = np.eye(self.dim_z) * R
+        return R
+
+    def _copy_state(self, *to):
+        """x_prior / P_prior ("prior") or x_post / P_post ("post") <- copies of x, P as they stand"""
+        for k in to:
+            setattr(self, "x_" + k, self.x.copy())
+            setattr(self, "P_" + k, self.P.copy())
+
+    def _skip_update(self):
+        """update(None) (:234-238)"""
+        self.z = self._no_z()
+        self._copy_state("post")
+
+    def _download(self, **tensors):
+        """attribute = tensor: the small results of a step as NumPy arrays"""
+        for k, t in tensors.items():
+            setattr(self, k, t.cpu().numpy())
+
+    def __repr__(self):
+        return "\n".join([f"{type(self).__name__} object (filterpy_amd, gfx950)"] +
+                         [f"{k} = {getattr(self, k)!r}" for k in self._REPR])
+
+
+class EnsembleKalmanFilter(_Ensemble):
+    """filterpy.kalman.EnsembleKalmanFilter (ensemble_kalman_filter.py:36-309) on the GPU: same attributes and defaults."""
+
+    def __init__(self, x, P, dim_z, dt, N, hx, fx, *, noise="numpy", vectorized=False, device_callables=False, layout="soa",
+                 generator=None):
+        self._ws = None
+        super().__init__((), x, P, dim_z, dt, N, hx, fx, noise, vectorized, device_callables, layout, generator)
+
+    def _given_x(self, x):
+        return x, len(x)
+
+    def _no_z(self):
+        return np.array([[None] * self.dim_z]).T
 
     def _draw(self, mean, cov, d, init=False):
         """one draw of the cycle -> (noise records, factor or None).  noise "device": standard normals and cov's factor; otherwise
@@ -189,14 +247,7 @@ class EnsembleKalmanFilter(object):
         self._sig_host = None
         self.x = x
         self.P = P
-        self.x_prior = self.x.copy()
-        self.P_prior = self.P.copy()
-        self.x_post = self.x.copy()
-        self.P_post = self.P.copy()
-
-    def _check_inv(self):
-        if self.inv is not np.linalg.inv:
-            raise NotImplementedError("EnsembleKalmanFilter.inv other than numpy.linalg.inv: the inverse is taken on the device")
+        self._copy_state("prior", "post")
 
     def _apply(self, fn, d, *args):
         """fx / hx as callables over the ensemble -> (N, d) device records (device_callables) or host array uploaded"""
@@ -215,17 +266,10 @@ class EnsembleKalmanFilter(object):
         """ensemble_kalman_filter.py:218-273.  z None: bookkeeping only (:234-238)."""
         import torch
         if z is None:
-            self.z = np.array([[None] * self.dim_z]).T
-            self.x_post = self.x.copy()
-            self.P_post = self.P.copy()
-            return
+            return self._skip_update()
         self._check_inv()
         n, m = self.dim_x, self.dim_z
-        if R is None:
-            R = self.R
-        if np.isscalar(R):
-            R = np.eye(m) * R
-        R = np.asarray(R, dtype=np.float64)
+        R = np.asarray(self._given_R(R), dtype=np.float64)
         if R.shape != (m, m):
             raise ValueError(f"R has shape {R.shape}, expected ({m}, {m})")
         za = np.asarray(z, dtype=np.float64).reshape(-1)
@@ -245,19 +289,14 @@ class EnsembleKalmanFilter(object):
         x = E.dev(np.asarray(self.x, dtype=np.float64).reshape(n))
         P = E.dev(np.asarray(self.P, dtype=np.float64).reshape(n, n))
         S, SI, K = (torch.empty(s, dtype=torch.float64, device=x.device) for s in ((m, m), (m, m), (n, m)))
-        st = torch.zeros(1, dtype=torch.int32, device=x.device)
+        st = status(1, x)
         E.enkf_update(self._desc(), E.dev(R), E.dev(za), noise, self._sig, x, P, self._workspace(), H=H, sigmas_h=sh,
                       factor=fac, S=S, SI=SI, K=K, status=st)
         self._sig_host = None
         E.raise_on_status(st, "EnsembleKalmanFilter.update (S is not positive definite)")
-        self.S = S.cpu().numpy()
-        self.SI = SI.cpu().numpy()
-        self.K = K.cpu().numpy()
-        self.x = x.cpu().numpy()
-        self.P = P.cpu().numpy()
+        self._download(S=S, SI=SI, K=K, x=x, P=P)
         self.z = deepcopy(z)
-        self.x_post = self.x.copy()
-        self.P_post = self.P.copy()
+        self._copy_state("post")
 
     def predict(self):
         """ensemble_kalman_filter.py:275-290"""
@@ -282,23 +321,15 @@ class EnsembleKalmanFilter(object):
         else:
             x = E.dev(np.asarray(self.x, dtype=np.float64).reshape(n))
         P = torch.empty((n, n), dtype=torch.float64, device=x.device)
-        st = torch.zeros(1, dtype=torch.int32, device=x.device)
+        st = status(1, x)
         E.enkf_predict(self._desc(), noise, self._sig, x, P, self._workspace(), F=F, factor=fac, status=st)
         self._sig_host = None
         E.raise_on_status(st, "EnsembleKalmanFilter.predict")
-        self.x = x.cpu().numpy()
-        self.P = P.cpu().numpy()
-        self.x_prior = np.copy(self.x)
-        self.P_prior = np.copy(self.P)
-
-    def __repr__(self):
-        return "\n".join(["EnsembleKalmanFilter object (filterpy_amd, gfx950)"] +
-                         [f"{k} = {getattr(self, k)!r}" for k in
-                          ("dim_x", "dim_z", "dt", "N", "layout", "noise", "x", "P", "x_prior", "P_prior", "Q", "R", "K", "S",
-                           "sigmas", "hx", "fx")])
+        self._download(x=x, P=P)
+        self._copy_state("prior")
 
 
-class EnsembleKalmanFilterBank(object):
+class EnsembleKalmanFilterBank(_Ensemble):
     """n_tracks independent ensemble Kalman filters of N members each (2 <= N <= 2048), stepped together: predict() is ONE launch
     for all ensembles (fk_enkf_bank_predict_f64) and update() is one (fk_enkf_bank_update_f64; csrc/enkf_bank.hip) -- one wave per
     ensemble up to N = 64, one workgroup per ensemble above.  The arithmetic and its order are EnsembleKalmanFilter's: on the same
@@ -337,51 +368,27 @@ class EnsembleKalmanFilterBank(object):
 
     def __init__(self, x, P, dim_z, dt, N, hx, fx, n_tracks, *, noise="numpy", vectorized=False, device_callables=False,
                  layout="soa", generator=None):
-        if dim_z <= 0:
-            raise ValueError('dim_z must be greater than zero')
-        if N < 2:
-            raise ValueError('N must be at least 2 (the covariances divide by N - 1)')
+        self.n_tracks = n_tracks
+        super().__init__((n_tracks,), x, P, dim_z, dt, N, hx, fx, noise, vectorized, device_callables, layout, generator)
+        self.status = np.zeros(n_tracks, dtype=np.int32)
+
+    _REPR = ("n_tracks",) + _Ensemble._REPR
+
+    def _check_size(self, N, lead):
         if N > E.ENKF_CHUNK:
             raise NotImplementedError(f"N = {N} > {E.ENKF_CHUNK} members per ensemble of a bank: use EnsembleKalmanFilter, one "
                                       "filter per ensemble")
-        if n_tracks < 1:
+        if lead[0] < 1:
             raise ValueError('n_tracks must be at least 1')
-        if layout not in E.LAYOUTS:
-            raise ValueError(f"layout must be one of {sorted(E.LAYOUTS)}")
-        if not (noise in ("numpy", "device") or callable(noise)):
-            raise ValueError('noise must be "numpy", "device" or a callable (mean, cov, N) -> (N, d)')
+
+    def _given_x(self, x):
         x = np.asarray(x, dtype=np.float64)
         if x.ndim not in (1, 2):
             raise ValueError('x must be (dim_x,) or (n_tracks, dim_x)')
-        dim_x = x.shape[-1]
-        if dim_x > 16 or dim_z > 8:
-            raise NotImplementedError("dim_x/dim_z outside the compiled range (dim_x <= 16, dim_z <= 8)")
-        self.dim_x = dim_x
-        self.dim_z = dim_z
-        self.dt = dt
-        self.N = N
-        self.n_tracks = n_tracks
-        self.hx = hx
-        self.fx = fx
-        self.noise = noise
-        self.vectorized = vectorized
-        self.device_callables = device_callables
-        self.layout = layout
-        self.generator = generator
-        B = n_tracks
-        self.K = np.zeros((B, dim_x, dim_z))
-        self.z = np.full((B, dim_z), None, dtype=object)
-        self.S = np.zeros((B, dim_z, dim_z))
-        self.SI = np.zeros((B, dim_z, dim_z))
-        self.status = np.zeros(B, dtype=np.int32)
-        self._sig = self._sig_host = None
+        return x, x.shape[-1]
 
-        self.initialize(x, P)
-        self.Q = np.eye(dim_x)
-        self.R = np.eye(dim_z)
-        self.inv = np.linalg.inv
-        self._mean = np.zeros(dim_x)
-        self._mean_z = np.zeros(dim_z)
+    def _no_z(self):
+        return np.full((self.n_tracks, self.dim_z), None, dtype=object)
 
     # -- shapes ---------------------------------------------------------------------------------------------------------------
     def _per_track(self, a, shape, name):
@@ -406,44 +413,6 @@ class EnsembleKalmanFilterBank(object):
         return dict(_desc(self.dim_x, self.dim_z, 0, self.N, 1, self.layout), model_mode=mode)
 
     # -- the ensembles ------------------------------------------------------------------------------------------------------
-    @property
-    def sigmas(self):
-        """the ensembles as an (n_tracks, N, dim_x) NumPy array: downloaded on first read after a step, then cached"""
-        if self._sig_host is None:
-            self._sig_host = E.from_records(self._sig, self.layout, 1, (self.dim_x,)).copy()
-        return self._sig_host
-
-    @sigmas.setter
-    def sigmas(self, value):
-        a = np.asarray(value, dtype=np.float64)
-        if a.shape != (self.n_tracks, self.N, self.dim_x):
-            raise ValueError(f"sigmas has shape {a.shape}, expected ({self.n_tracks}, {self.N}, {self.dim_x})")
-        self._sig = E.to_records(a, self.layout, 1)
-        self._sig_host = None
-
-    @property
-    def sigmas_device(self):
-        """the device tensor, in `layout`: (n_tracks, dim_x, N) for 'soa', (n_tracks, N, dim_x) for 'aos'"""
-        return self._sig
-
-    def _members(self):
-        """the device tensor as an (n_tracks, N, dim_x) view"""
-        return self._sig.transpose(1, 2) if self.layout == "soa" else self._sig
-
-    def _records(self, t, d):
-        """an (n_tracks, N, d) array or tensor -> device records in `layout`"""
-        import torch
-        shape = (self.n_tracks, self.N, d)
-        if isinstance(t, torch.Tensor):
-            t = E.dev(t)
-            if tuple(t.shape) != shape:
-                raise ValueError(f"expected an {shape} tensor, got {tuple(t.shape)}")
-            return t.transpose(1, 2).contiguous() if self.layout == "soa" else t
-        a = np.asarray(t, dtype=np.float64)
-        if a.shape != shape:
-            raise ValueError(f"expected an {shape} array, got {a.shape}")
-        return E.to_records(a, self.layout, 1)
-
     def _draw(self, mean, cov, d, present=None, init=False):
         """one draw of the cycle for the tracks that take part -> (noise records, per-track-or-shared factor or None).  mean: (d,)
         or (n_tracks, d); cov: (d, d) or (n_tracks, d, d)"""
@@ -492,14 +461,7 @@ class EnsembleKalmanFilterBank(object):
         self._sig_host = None
         self.x = self._full(x, (n,))
         self.P = self._full(P, (n, n))
-        self.x_prior = self.x.copy()
-        self.P_prior = self.P.copy()
-        self.x_post = self.x.copy()
-        self.P_post = self.P.copy()
-
-    def _check_inv(self):
-        if self.inv is not np.linalg.inv:
-            raise NotImplementedError("EnsembleKalmanFilterBank.inv other than numpy.linalg.inv: the inverse is taken on the device")
+        self._copy_state("prior", "post")
 
     def _apply(self, fn, d, *args, present=None):
         """fx / hx as callables over the ensembles -> (n_tracks, N, d) device records (device_callables) or host array"""
@@ -547,16 +509,9 @@ class EnsembleKalmanFilterBank(object):
                     raise ValueError(f"z[{b}] has {zb.size} entries, expected dim_z = {m}")
                 za[b] = zb
         if not present.any():
-            self.z = np.full((B, m), None, dtype=object)
-            self.x_post = self.x.copy()
-            self.P_post = self.P.copy()
-            return
+            return self._skip_update()
         self._check_inv()
-        if R is None:
-            R = self.R
-        if np.isscalar(R):
-            R = np.eye(m) * R
-        R = self._per_track(R, (m, m), "R")
+        R = self._per_track(self._given_R(R), (m, m), "R")
         H = self._matrix(self.hx, (m, n), "hx")
         sh = None if H is not None else self._apply(self.hx, m, present=present)
         noise, fac = self._draw(self._mean_z, R, m, present)             # (after every hx call, :263)
@@ -567,23 +522,17 @@ class EnsembleKalmanFilterBank(object):
         P = E.dev(self._full(self._per_track(self.P, (n, n), "P"), (n, n)))
         S, SI, K = (E.dev(self._full(self._per_track(a, s, k), s)) for a, s, k in
                     ((self.S, (m, m), "S"), (self.SI, (m, m), "SI"), (self.K, (n, m), "K")))
-        st = torch.zeros(B, dtype=torch.int32, device=x.device)
+        st = status(B, x)
         mk = None if present.all() else torch.as_tensor(present.astype(np.uint8), device=x.device)
         E.enkf_bank_update(self._desc(mode), B, Rd, E.dev(za), noise, self._sig, x, P, H=H, sigmas_h=sh, mask=mk, factor=fac,
                            S=S, SI=SI, K=K, status=st)
         self._sig_host = None
         self.status = st.cpu().numpy()
         E.raise_on_status(st, "EnsembleKalmanFilterBank.update (S is not positive definite)")
-        self.S = S.cpu().numpy()
-        self.SI = SI.cpu().numpy()
-        self.K = K.cpu().numpy()
-        self.x = x.cpu().numpy()
-        self.P = P.cpu().numpy()
-        zo = np.full((B, m), None, dtype=object)
-        zo[present] = za[present]
-        self.z = zo
-        self.x_post = self.x.copy()
-        self.P_post = self.P.copy()
+        self._download(S=S, SI=SI, K=K, x=x, P=P)
+        self.z = self._no_z()
+        self.z[present] = za[present]
+        self._copy_state("post")
 
     def predict(self):
         """ensemble_kalman_filter.py:275-290 for every track"""
@@ -601,18 +550,10 @@ class EnsembleKalmanFilterBank(object):
             x = E.dev(self._full(self._per_track(self.x, (n,), "x"), (n,)))
         mode, (F, fac) = self._model([F, fac])
         P = torch.empty((B, n, n), dtype=torch.float64, device=x.device)
-        st = torch.zeros(B, dtype=torch.int32, device=x.device)
+        st = status(B, x)
         E.enkf_bank_predict(self._desc(mode), B, noise, self._sig, x, P, F=F, factor=fac, status=st)
         self._sig_host = None
         self.status = st.cpu().numpy()
         E.raise_on_status(st, "EnsembleKalmanFilterBank.predict")
-        self.x = x.cpu().numpy()
-        self.P = P.cpu().numpy()
-        self.x_prior = np.copy(self.x)
-        self.P_prior = np.copy(self.P)
-
-    def __repr__(self):
-        return "\n".join(["EnsembleKalmanFilterBank object (filterpy_amd, gfx950)"] +
-                         [f"{k} = {getattr(self, k)!r}" for k in
-                          ("n_tracks", "dim_x", "dim_z", "dt", "N", "layout", "noise", "x", "P", "x_prior", "P_prior", "Q", "R", "K",
-                           "S", "sigmas", "hx", "fx")])
+        self._download(x=x, P=P)
+        self._copy_state("prior")
