@@ -704,7 +704,20 @@ __device__ unsigned long long *g_dbg_tl;   // [Fn * nch][16] wall-clock stamps (
 #define OP_COUNT(slot, n) do { if (threadIdx.x == 0) t_acc[slot] += (n); } while (0)
 #define OP_CLOCK_FLUSH() do { if (threadIdx.x == 0) for (int q_ = 0; q_ < OP_PHASE_SLOTS; ++q_) \
         if (t_acc[q_]) atomicAdd(&fk_op_phase[q_][blockIdx.x % OP_PHASE_BUCKETS], (unsigned long long)t_acc[q_]); } while (0)
+// how a kernel's accumulators reach the functions it shares with the others: two more parameters, in this build only.  A caller
+// that keeps no clocks of that kind (op_chunk_slow stamps a timeline instead: OP_UNTIMED; resample_local_kernel clocks around its
+// calls: OP_NO_TIMERS) hands over a null pointer and OP_CLOCK_IF_TIMED does nothing.
+#define OP_TIMERS_DECL , long long *t_acc, long long &t_prev
+#define OP_TIMERS , t_acc, t_prev
+#define OP_NO_TIMERS , nullptr, t_prev
+#define OP_UNTIMED() long long *t_acc = nullptr; long long t_prev = 0
+#define OP_CLOCK_IF_TIMED(slot) do { if (t_acc) OP_CLOCK(slot); } while (0)
 #else
+#define OP_TIMERS_DECL
+#define OP_TIMERS
+#define OP_NO_TIMERS
+#define OP_UNTIMED() do { } while (0)
+#define OP_CLOCK_IF_TIMED(slot) do { } while (0)
 #define OP_CLOCK_START() do { } while (0)
 #define OP_CLOCK(slot) do { } while (0)
 #define OP_COUNT(slot, n) do { } while (0)
@@ -735,6 +748,509 @@ __device__ __forceinline__ void init_window(int *win, int tid)
 {
     FK_UNROLL for (int g = 0; g < 3; ++g) *reinterpret_cast<i32x4 *>(&win[12 * tid + 4 * g]) = i32x4{-1, -1, -1, -1};
 }
+
+// ---- the phases of one chunk, stated once: resample_onepass_kernel (its prologue and op_resolve_chunk), op_chunk_slow (through
+// op_resolve_chunk) and resample_local_kernel all resolve a chunk of OP_TILE weights with these -------------------------------
+template <bool STRATIFIED>
+struct ChunkCtx {       // what the slot boundaries of one filter are taken against
+    long Np;
+    double Nd, halfNd, u_sys;
+    const double *u_str;
+#ifdef FK_OP_CLOCKS
+    long dbg_at = -1;   // where the chunk's first weight goes in the g_dbg_cs / g_dbg_n dump (-1: this caller dumps nothing)
+    int dbg_len = 0;
+#endif
+};
+
+template <bool STRATIFIED>
+__device__ __forceinline__ ChunkCtx<STRATIFIED> chunk_ctx(const OpArgs &a, const int f, const long dbg_chunk = -1)
+{
+    ChunkCtx<STRATIFIED> cx;
+    cx.Np = a.Np;
+    cx.Nd = (double)a.Np;
+    cx.halfNd = 0.5 * cx.Nd;
+    cx.u_sys = STRATIFIED ? 0.0 : a.u[f];
+    cx.u_str = STRATIFIED ? a.u + (long)f * a.Np : nullptr;
+#ifdef FK_OP_CLOCKS
+    if (dbg_chunk >= 0) {                                                  // (the one-pass kernels: one chunk per context)
+        const long base = dbg_chunk * OP_TILE;
+        cx.dbg_at = (long)f * a.Np + base;
+        cx.dbg_len = (int)((a.Np - base) < OP_TILE ? (a.Np - base) : OP_TILE);
+    }
+#endif
+    return cx;
+}
+
+// n(c): the first slot whose position is not below the running sum c
+template <bool STRATIFIED>
+__device__ __forceinline__ int chunk_boundary(const double c, const ChunkCtx<STRATIFIED> &cx)
+{
+    return n_boundary_fast<STRATIFIED>(c, (int)cx.Np, cx.Nd, cx.halfNd, cx.u_sys, cx.u_str);
+}
+
+// the chunk's sum -- per-wave partials through `part`, ONE barrier -- and the verdict on its weights: any_bad = a negative one, a
+// NaN, an Inf or an absurdly large sum
+__device__ __forceinline__ double chunk_sum(const double (&w8)[OP_ITEMS], double (&part)[OP_THREADS / 64], const int lane, const int wave,
+                                            bool &any_bad)
+{
+    double s = 0.0, mn = 0.0;
+    FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
+        s += w8[q];
+        mn = w8[q] < mn ? w8[q] : mn;                                      // a negative weight (NaN / Inf show in the sum)
+    }
+    s = lane_bcast(wave_incl_sum(s), 63);
+    if (lane == 0) part[wave] = s;
+    const int any_neg = __syncthreads_or(mn < 0.0 ? 1 : 0);
+    const double S = (part[0] + part[1]) + (part[2] + part[3]);
+    any_bad = any_neg || !(S < 0x1p1000);
+    return S;
+}
+
+// increments in a known binade (ulp 2^eu; fk_exact_scan.hpp, fast_inc): inc = floor(w / ulp + 1/2) unless the remainder is
+// exactly half an ulp (`tie`).  E[q] = inclusive sums of the thread's increments; returns the last one.
+__device__ __forceinline__ double thread_increments(const double (&w8)[OP_ITEMS], const int eu, double (&E)[OP_ITEMS], bool &tie)
+{
+    double run = 0.0;
+    FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
+        const double x = scale2(w8[q], -eu) + 0.5;
+        const double i = floor(x);
+        tie = tie || (i == x);
+        run += i;
+        E[q] = run;
+    }
+    return run;
+}
+
+// ... and across the chunk (one barrier, through sh.wsum): excl = the increments before the thread's, I = the chunk's.  False: the
+// chunk holds a tie, or its sums reach 2^53 (which is also where t + 1/2 stops being exact, and then the test fires by itself) --
+// such a chunk leaves the integer path.
+__device__ __forceinline__ bool chunk_increments(OpShared &sh, const double (&w8)[OP_ITEMS], const int eu, const int lane, const int wave,
+                                                 double (&E)[OP_ITEMS], double &excl, double &I)
+{
+    bool tie = false;
+    const double run = thread_increments(w8, eu, E, tie);
+    const double winc = wave_incl_sum(run);
+    if (lane == 63) sh.wsum[wave] = winc;
+    const int any_tie = __syncthreads_or(tie ? 1 : 0);
+    excl = winc - run;                                                     // exact: everything is an integer < 2^53 ...
+    I = 0.0;
+    FK_UNROLL for (int wv = 0; wv < OP_THREADS / 64; ++wv) {
+        if (wv < wave) excl += sh.wsum[wv];
+        I += sh.wsum[wv];
+    }
+    return !any_tie && I < 0x1p53;                                         // ... or this says so
+}
+
+// slot boundaries of a chunk that stayed inside the binade of its carry-in: weight j owns the slots [n_{j-1}, n_j), n_j = n(cs_j)
+// (fk_resample_math.hpp).  cs_j = (C0 + excl + E_j) ulp exactly, so N cs_j - u = fma(E_j, N ulp, C0 N ulp - u): ONE fma per
+// weight gives the estimate whose ceiling is n_j whenever it is not within eps of an integer (n_boundary_fast's argument: here two
+// roundings of 2^-22 slots each, the same budget); the rare rest takes the exact tests on cs_j.
+template <bool STRATIFIED>
+__device__ __forceinline__ void quick_boundaries(const double (&E)[OP_ITEMS], double excl, double c_in, int eu,
+                                                 const ChunkCtx<STRATIFIED> &cx, int (&nb)[OP_ITEMS])
+{
+    const double ulp = scale2(1.0, eu), C0 = scale2(c_in, -eu), Nu = scale2(cx.Nd, eu);
+    const double K = __builtin_fma(C0, Nu, STRATIFIED ? 0.0 : -cx.u_sys);
+    unsigned unsure = 0;
+    FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
+        const double Et = excl + E[q];                                     // exact
+        const double e = __builtin_fma(Et, Nu, K);
+        // floor(e) + 1 without a v_floor_f64 / v_cvt_i32_f64 pair: m = e + 1.5 2^52 holds the nearest integer
+        // of e in its low mantissa bits (two's complement; -1 < e < Nd < 2^31 where the result is used), dd = e - nearest
+        const double m = e + 0x1.8p52;
+        const double dd = e - (m - 0x1.8p52);                              // exact, |dd| <= 1/2
+        const int ri = (int)(unsigned)double_to_bits(m);
+        bool sure = fabs(dd) > N_BOUNDARY_EPS && e < cx.Nd;                // (= fr in (eps, 1 - eps))
+        int n = ri + (dd < 0.0 ? 0 : 1);
+        if (STRATIFIED) {
+            const int fl = ri - (dd < 0.0 ? 1 : 0);
+            const double fr = dd < 0.0 ? dd + 1.0 : dd;                    // e - floor(e), exact
+            const double uf = cx.u_str[e < cx.Nd ? fl : 0];                // e >= 0 here
+            const double gap = uf - fr;
+            sure = sure && (gap > N_BOUNDARY_EPS || gap < -N_BOUNDARY_EPS);
+            n = fl + (gap > 0.0 ? 0 : 1);
+        }
+        unsure |= sure ? 0u : (1u << q);
+        nb[q] = n;
+    }
+    if (unsure) {                                                          // about one weight in 10^5: the exact tests
+        // ONE inlined copy in a rolled loop; E[q] / nb[q] are picked and put back with selects (registers
+        // cannot be indexed)
+        _Pragma("nounroll") for (int q = 0; q < OP_ITEMS; ++q) {
+            if (!(unsure & (1u << q))) continue;
+            double Eq = E[0];
+            FK_UNROLL for (int r = 1; r < OP_ITEMS; ++r) Eq = (q == r) ? E[r] : Eq;
+            const int n = n_boundary<STRATIFIED>((C0 + (excl + Eq)) * ulp, (int)cx.Np, cx.Nd, cx.halfNd, cx.u_sys, cx.u_str);
+            FK_UNROLL for (int r = 0; r < OP_ITEMS; ++r) nb[r] = (q == r) ? n : nb[r];
+        }
+    }
+#ifdef FK_OP_CLOCKS
+    FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
+        const int j = (int)threadIdx.x * OP_ITEMS + q;
+        if (g_dbg_cs && cx.dbg_at >= 0 && j < cx.dbg_len) {
+            g_dbg_cs[cx.dbg_at + j] = (C0 + (excl + E[q])) * ulp;
+            g_dbg_n[cx.dbg_at + j] = nb[q];
+        }
+    }
+#endif
+}
+
+// slot boundaries from the cumulative sums a scan left in the tile (slots >= len take the carry-out: no slots).  Each thread reads
+// back only its own slots, behind the scan's final barrier; n_j goes into the low half of cs_j's slot so that the loop stays rolled.
+template <bool STRATIFIED>
+__device__ __forceinline__ void tile_boundaries(OpShared &sh, int len, double c_out, const ChunkCtx<STRATIFIED> &cx, int tid,
+                                                int (&nb)[OP_ITEMS])
+{
+    int *nslot = reinterpret_cast<int *>(&sh.tile[pad8(tid * OP_ITEMS)]);
+    _Pragma("nounroll") for (int q = 0; q < OP_ITEMS; ++q) {
+        const int j = tid * OP_ITEMS + q;
+        const double c = j < len ? sh.tile[pad8(j)] : c_out;
+        const int n = chunk_boundary(c, cx);
+        nslot[2 * q] = n;
+#ifdef FK_OP_CLOCKS
+        if (g_dbg_cs && cx.dbg_at >= 0 && j < len) {
+            g_dbg_cs[cx.dbg_at + j] = c;
+            g_dbg_n[cx.dbg_at + j] = n;
+        }
+#endif
+    }
+    FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) nb[q] = nslot[2 * q];
+}
+
+// emission: the heads (the slot where each non-empty run starts; boundaries are non-decreasing for valid input) go into windows of
+// OP_WIN slots, an inclusive max-scan fills the runs, the window leaves as coalesced 16-byte stores.  Returns the chunk's last
+// boundary.  (Slot numbers fit an int: Np < 2^31; everything about a window is wave-uniform and lives in SGPRs.)
+// win_ready: the window is initialised and nothing has overwritten it (a scan in the tile does).
+__device__ __forceinline__ int emit_slots(OpShared &sh, int *win, const int (&nb)[OP_ITEMS], int u_lo, long base,
+                                          int32_t *of, int tid, bool win_ready OP_TIMERS_DECL)
+{
+    const int lane = tid & 63, wave = tid >> 6;
+    sh.nlast[tid] = nb[OP_ITEMS - 1];
+    __syncthreads();                                                                          // (E)
+    int nprev = tid == 0 ? u_lo : sh.nlast[tid - 1];
+    const int u_hi = __builtin_amdgcn_readfirstlane(sh.nlast[OP_THREADS - 1]);
+    int head[OP_ITEMS];
+    FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
+        head[q] = nb[q] > nprev ? nprev : -1;
+        nprev = nb[q] > nprev ? nb[q] : nprev;
+    }
+    OP_CLOCK_IF_TIMED(6);                                                  // boundaries
+    const int mis = (int)(((uintptr_t)of >> 2) & 3);
+    int seed = -1;
+    for (int wb = u_lo - ((mis + u_lo) & 3); u_hi > u_lo && wb < u_hi; wb += OP_WIN) {        // uniform
+        if (!win_ready) {
+            __syncthreads();                                               // everybody is done with the tile / the last window
+            init_window(win, tid);
+            __syncthreads();
+        }
+        win_ready = false;
+        int have = 0;
+        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
+            const unsigned h = (unsigned)(head[q] - wb);                   // a head below wb wraps to a huge number
+            if (head[q] >= 0 && h < (unsigned)OP_WIN) {
+                win[h] = (int)base + tid * OP_ITEMS + q;
+                have = 1;
+            }
+        }
+        const int any_head = __syncthreads_or(have);                                          // (G)
+        const int lim = u_hi - wb;                                         // slots [max(first, 0), lim) are ours
+        const int first = u_lo - wb;
+        int32_t *ow = of + wb;                                             // uniform; 16-byte aligned
+        const int s0 = 12 * tid;
+        int x[12];
+        if (any_head) {                                                    // uniform
+            FK_UNROLL for (int g = 0; g < 3; ++g) {
+                const i32x4 t = *reinterpret_cast<const i32x4 *>(&win[s0 + 4 * g]);
+                x[4 * g + 0] = t.x;
+                x[4 * g + 1] = t.y;
+                x[4 * g + 2] = t.z;
+                x[4 * g + 3] = t.w;
+            }
+            FK_UNROLL for (int e = 1; e < 12; ++e) x[e] = x[e] > x[e - 1] ? x[e] : x[e - 1];
+            const int wincl = wave_incl_max(x[11]);
+            if (lane == 63) sh.wmax[wave] = wincl;
+            __syncthreads();
+            const int up = __shfl_up(wincl, 1, 64);
+            int pre = (lane == 0 || up < seed) ? seed : up;               // everything before this thread, this wave
+            FK_UNROLL for (int wv = 0; wv < OP_THREADS / 64; ++wv) {
+                const int t = sh.wmax[wv];
+                if (wv < wave) pre = pre > t ? pre : t;
+                seed = seed > t ? seed : t;                                // every thread: running max after this window
+            }
+            FK_UNROLL for (int e = 0; e < 12; ++e) x[e] = x[e] > pre ? x[e] : pre;
+        } else {
+            // the whole window lies inside one run (a weight owning more than OP_WIN slots): constant fill
+            FK_UNROLL for (int e = 0; e < 12; ++e) x[e] = seed;
+        }
+        if (s0 < lim) {
+            FK_UNROLL for (int g = 0; g < 3; ++g) {
+                const int s4 = s0 + 4 * g;
+                if (s4 >= first && s4 + 3 < lim) *reinterpret_cast<i32x4 *>(&ow[s4]) = i32x4{x[4 * g], x[4 * g + 1], x[4 * g + 2], x[4 * g + 3]};
+                else {
+                    FK_UNROLL for (int e = 0; e < 4; ++e)
+                        if (s4 + e >= first && s4 + e < lim) ow[s4 + e] = x[4 * g + e];
+                }
+            }
+        }
+    }
+    return u_hi;
+}
+
+// the weights of a chunk: every thread reads its eight CONSECUTIVE weights straight from HBM (a wave covers 4 KiB with four 16-byte
+// loads per lane: every byte of every line is used, nothing is staged or transposed through LDS); +0.0 behind the vector's end
+__device__ __forceinline__ void load_chunk(double (&w8)[OP_ITEMS], const double *wf, long base, long Np, int tid)
+{
+    const int len = (int)((Np - base) < OP_TILE ? (Np - base) : OP_TILE);
+    const double *src = wf + base + tid * OP_ITEMS;
+    if (len == OP_TILE && (((uintptr_t)(wf + base)) & 15) == 0) {                              // uniform
+        FK_UNROLL for (int q = 0; q < OP_ITEMS; q += 2) {
+            const f64x2 t = *reinterpret_cast<const f64x2 *>(src + q);
+            w8[q] = t.x;
+            w8[q + 1] = t.y;
+        }
+    } else if (len == OP_TILE) {
+        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) w8[q] = src[q];
+    } else {
+        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
+            const int j = tid * OP_ITEMS + q;
+            const double t = wf[base + (j < len ? j : 0)];
+            w8[q] = j < len ? t : 0.0;
+        }
+    }
+}
+
+// the end of a vector: positions >= cumsum[-1] (the reference raises IndexError, resampling.py:109,145) take the last index
+__device__ __forceinline__ void fill_behind_cumsum(int32_t *of, const int u_hi, const long Np, const int tid)
+{
+    for (long i = (long)u_hi + tid; i < Np; i += OP_THREADS) of[i] = (int32_t)(Np - 1);
+}
+
+// ---- one chunk of the one-pass kernels, from its weights to its slots: stage 1 -> stage 2 -> boundaries (quick / zeros / exact
+// scan) -> emission -> end of the vector.  Both kernels resolve a chunk with THIS text:
+//   LB = false: round 3's chunk, what resample_onepass_kernel does behind its speculation (hit: the speculation has already found
+//        the exact carry-in -- E, excl, I, eu are the caller's, sh.bc_d[1] / sh.bc_i[3..4] hold c_in, quick = 1 and the first slot --
+//        and the chunk goes straight to its boundaries; else the two stages run and set them): 16-wide look-backs, general_cumsum
+//        directly for what leaves the integer path;
+//   LB = true: round 6's additions, for the chunks resample_onepass2_kernel's fast path declines (op_chunk_slow; hit = false),
+//        chosen by the launcher's lb_mode: & 2 a crossing chunk adds up increment sums in the binade of its carry-in, & 4 the exact
+//        scan is prepared on the approximate carry-in and only its chain waits for the exact one, & 8 64-wide look-back steps; and
+//        the one-round segmented_cumsum before general_cumsum.
+// In: the chunk's weights (+0.0 behind the end of the vector), their sum S (NaN if any_bad), the window initialised.
+// Instrumentation (-DFK_OP_CLOCKS only): LB = false accumulates phase clocks (OP_CLOCK / OP_COUNT: tools/op_phase.py), LB = true
+// stamps the chunk's timeline (OP_STAMP / OP_NOTE: tools/op_timeline.py) -- OP_PHASE(clock slot, stamp slot) is a point both mark.
+#define OP_PHASE(clock_slot, stamp_slot) do { if constexpr (LB) OP_STAMP(stamp_slot); else OP_CLOCK(clock_slot); } while (0)
+template <bool STRATIFIED, bool LB>
+__device__ __forceinline__ void op_resolve_chunk(OpShared &sh, const OpArgs &a, const ChunkCtx<STRATIFIED> &cx, const int f, const int k,
+                                                 const double (&w8)[OP_ITEMS], const double S, const bool any_bad, const bool hit,
+                                                 double (&E)[OP_ITEMS], double &excl, double &I, int &eu, const int lb_mode OP_TIMERS_DECL)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long Np = a.Np, nch = a.nch;
+    int32_t *of = a.idx + (long)f * Np;
+    OpDesc *d = a.desc + (long)f * nch;
+    unsigned *abort_word = &a.ctl->abort;
+    const long base = (long)k * OP_TILE;
+    const int len = (int)((Np - base) < OP_TILE ? (Np - base) : OP_TILE);
+    // (lb_mode & 8: 64 predecessors per look-back step instead of 16 -- calls with few long vectors walk hundreds of chunks back.
+    //  Measured with and without, and with s_setprio 3 on this path: 1 x 8e6 108 / 110 / 111 us, nothing -- profiles/r06/onepass/r06o)
+    const int lbw = (LB && (lb_mode & 8)) ? 64 : OP_LB;
+    bool at_start = false;
+    SegRegs R;
+    bool prepared = false, scan_tried = false;
+    if (!hit) {
+    // ---- stage 1: approximate carry-in --------------------------------------------------------------------
+    if (wave == 0) {
+        double A = 0.0;
+        if (k > 0) {
+            if (lane == 0) st_agent(&d[k].approx, pack_approx(S, 1));
+            A = lookback_approx(d, k, lane, abort_word, lbw);
+        }
+        if (lane == 0) {
+            st_agent(&d[k].approx, pack_approx(A + S, 2));
+            sh.bc_d[0] = A;
+        }
+    }
+    __syncthreads();                                                                          // (B)
+    OP_PHASE(2, 6);                                                        // stage 1
+    const double A = sh.bc_d[0];
+
+    // ---- what stage 1 tells this chunk --------------------------------------------------------------------
+    const bool poison = !(A >= 0.0 && S >= 0.0 && A + S < 0x1p1000);
+    if (poison) {                                                          // uniform
+        // a weight this path does not take (negative, NaN, huge) here or upstream: the whole filter is redone by
+        // resample_literal_kernel; successors only need to learn that quickly
+        if (tid == 0) {
+            publish_carry(&d[k], __builtin_nan(""));
+            if (any_bad) __hip_atomic_store(&a.bad[f], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (a.status && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                atomicOr(&a.status[f], ST_INTERNAL);
+        }
+        return;
+    }
+    // A == 0 means EXACTLY: every weight before this chunk is +0.0 (they are all >= 0), so the carry-in is 0 and
+    // needs no stage 2; with S == 0 as well the chunk is empty-handed: carry-out 0, no slots
+    at_start = (k == 0) || (A == 0.0);
+    bool clean = false;
+    {
+        const double lo = A * (1.0 - a.delta), hi = (A + S) * (1.0 + a.delta);
+        if (lo > OP_SANE_LO && hi < OP_SANE_HI && ulp_exp(lo) == ulp_exp(hi)) {
+            clean = true;
+            eu = ulp_exp(lo);
+        }
+    }
+    // increments in the promised binade; a chunk with a tie, or whose sums reach 2^53, leaves this path
+    excl = 0.0;
+    I = 0.0;
+    bool fast = false;
+    if (clean) {                                                           // uniform
+        fast = chunk_increments(sh, w8, eu, lane, wave, E, excl, I);                          // (C)
+    } else {
+        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) E[q] = 0.0;
+    }
+    if constexpr (!LB) OP_CLOCK(3);                                        // increments
+
+    if constexpr (LB) {
+    // ---- a chunk that needs the general scan prepares it NOW (lb_mode & 4): the weights into the tile, seg_prepare on the
+    // APPROXIMATE carry-in of stage 1 (relative error <= a.delta; exactly 0 at the start of a vector) -- all of this before the
+    // exact carry-in has arrived, while the chunks below are still being resolved.  What is left behind the carry is
+    // seg_chain, a few dependent adds by wave 0, and the carry-out goes out at once: with few long vectors every crossing of
+    // a binade and every tie-holder sits on the one chain all later chunks wait for, and it used to hold that chain for a
+    // reload of its weights, five barriers and the whole scan -- 7 us per crossing, 19 crossings in a row at 1 x 2e6
+    // (tools/op_timeline.py; profiles/r06/onepass/timeline_before.txt).
+    if (!fast && (lb_mode & 4) && !(at_start && S == 0.0)) {               // uniform
+        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) sh.tile[pad8(tid * OP_ITEMS + q)] = w8[q];   // (0.0 behind len)
+        __syncthreads();
+        scan_tried = true;
+        prepared = seg_prepare<true>(sh, len, at_start ? 0.0 : A, (at_start ? 0.0 : a.delta) + 0x1p-38, R);
+#ifdef FK_OP_CLOCKS
+        {   // (tools/op_timeline.py: core clocks / 16 between the barriers of seg_prepare, 16 bits each)
+            const SegShared &sg = sh.seg;
+            auto d16 = [](long long d) -> unsigned long long { d >>= 4; return (unsigned long long)(d < 0 ? 0 : (d > 65535 ? 65535 : d)); };
+            OP_NOTE(2, d16(sg.dbg_t[0] - sg.dbg_in) | (d16(sg.dbg_t[1] - sg.dbg_t[0]) << 16) | (d16(sg.dbg_t[2] - sg.dbg_t[1]) << 32) | (d16(sg.dbg_t[3] - sg.dbg_t[2]) << 48));
+        }
+#endif
+    }
+    OP_STAMP(7);
+    }   // LB
+    // ---- stage 2: exact carry-in ---------------------------------------------------------------------------
+    if (wave == 0) {
+        double c_in = 0.0;
+        bool ok = true;
+        if (!at_start) {
+            if (fast && lane == 0) st_agent(&d[k].exact, pack_exact(1, eu, I));
+            // (lb_mode & 2: a chunk that does NOT stay inside one binade -- a crossing -- still knows the binade of its carry-in from
+            //  stage 1, and may add up the predecessors' increment sums in THAT binade down to the nearest carry-out like anybody
+            //  else (the argument of lookback_exact is about the chunks in between, not about this one) instead of waiting for
+            //  chunk k-1 to see that carry, add the same sums and publish: one global round trip less per binade on the chain
+            //  every chunk of the binade above waits for)
+            bool lb_ok = fast;
+            int lb_eu = eu;
+            if (LB && !fast && (lb_mode & 2)) {
+                const double lo = A * (1.0 - a.delta), hi = A * (1.0 + a.delta);
+                if (lo > OP_SANE_LO && hi < OP_SANE_HI && ulp_exp(lo) == ulp_exp(hi)) {
+                    lb_ok = true;
+                    lb_eu = ulp_exp(lo);
+                }
+            }
+            c_in = lookback_exact(d, k, lb_ok, lb_eu, lane, abort_word, ok, lbw);
+        }
+        // carry-out of a chunk that stayed inside its binade: known right now, successors need not wait for the scan
+        int quick = 0;
+        if (ok && fast && c_in > OP_SANE_LO && c_in < OP_SANE_HI && ulp_exp(c_in) == eu) {
+            const double Cout = scale2(c_in, -eu) + I;
+            if (Cout < 0x1p53) {
+                quick = 1;
+                if (lane == 0) publish_carry(&d[k], scale2(Cout, eu));
+            }
+        }
+        if (ok && at_start && S == 0.0) {
+            quick = 2;                                                     // still nothing but zeros
+            if (lane == 0) publish_carry(&d[k], 0.0);
+        }
+        if constexpr (LB) {
+        if (ok && prepared && sh.seg.fail == 0) {                          // (behind seg_prepare's last barrier: every thread's verdict)
+            bool failed;
+            const double c_out = seg_chain(sh, c_in, R.D, R.ptotal, lane, failed);
+            if (!failed && lane == 0) publish_carry(&d[k], c_out);
+            OP_STAMP(14);
+        }
+        }
+        // first slot of this chunk: everything below n(carry-in) belongs to earlier chunks
+        const int out_lo = at_start ? 0 : chunk_boundary(c_in, cx);
+        if (lane == 0) {
+            sh.bc_d[1] = c_in;
+            sh.bc_i[3] = ok ? quick : -1;
+            sh.bc_i[4] = out_lo;
+        }
+    }
+    __syncthreads();                                                                          // (D)
+    }   // !hit
+    const double c_in = sh.bc_d[1];
+    const int quick = __builtin_amdgcn_readfirstlane(sh.bc_i[3]);
+    const int u_lo = __builtin_amdgcn_readfirstlane(sh.bc_i[4]);
+    OP_PHASE(4, 8);                                                        // stage 2
+    if constexpr (!LB) OP_COUNT(8 + (quick < 0 ? 3 : quick), 1);           // 8: general, 9: quick, 10: zeros
+    if (quick < 0) {                                                       // abort: a predecessor never published
+        if (tid == 0 && a.status) atomicOr(&a.status[f], ST_INTERNAL);
+        return;
+    }
+
+    // ---- slot boundaries ----
+    int nb[OP_ITEMS];
+    bool win_ready = true;
+    if (quick == 1) {                                                      // uniform
+        quick_boundaries<STRATIFIED>(E, excl, c_in, eu, cx, nb);
+        if constexpr (!LB) OP_CLOCK(5);
+    } else if (quick == 2) {
+        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) nb[q] = 0;
+        if constexpr (!LB) OP_CLOCK(5);
+    } else {
+        double c_out = 0.0;
+        if (LB && prepared && sh.seg.fail == 0) {                          // uniform (behind barrier (D))
+            seg_finish(sh, len, R);
+            c_out = sh.seg.carry_out;                                      // (published by wave 0 the moment it was known)
+        } else {
+            // general scan: the weights into the padded LDS tile the scan works in (a prepared scan that declined left them there)
+            // (LB = false reads them once more, from L2: the registers of round 3's kernel held across both look-backs for this rare
+            //  branch took its four speculating forms from 92-94 VGPRs and no scratch to 96 and 48 B, 24-26 spilled registers)
+            if (!prepared) {
+                if constexpr (LB) __syncthreads();                         // (round 3's kernel never had this one: the window it
+                                                                           //  overwrites was last touched in front of barrier (A))
+                FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
+                    const int j = tid * OP_ITEMS + q;
+                    sh.tile[pad8(j)] = LB ? w8[q] : (j < len ? a.w[(long)f * Np + base + j] : 0.0);
+                }
+            }
+            __syncthreads();
+            // (round 6: the one-round scan first -- binades predicted for all elements at once, then verified; round 3 goes straight
+            //  to general_cumsum, one block scan and four barriers per binade the running sum passes through: ~45 k clocks for the
+            //  first chunk of a vector, ~20 k for a crossing)
+            bool scanned = false;
+            if constexpr (LB) scanned = !scan_tried && segmented_cumsum(sh, len, c_in, &c_out);
+            if (!scanned) c_out = general_cumsum(sh, len, c_in);
+            if (tid == 0) publish_carry(&d[k], c_out);
+        }
+        OP_PHASE(5, 9);                                                    // exact scan
+        if constexpr (LB) OP_NOTE(15, (prepared ? 1 : 0) | (sh.seg.fail ? 2 : 0) | ((unsigned)R.D << 8));
+        tile_boundaries<STRATIFIED>(sh, len, c_out, cx, tid, nb);
+        win_ready = false;                                                 // the tile overwrote the window
+    }
+    const int u_hi = emit_slots(sh, sh.win(), nb, u_lo, base, of, tid, win_ready OP_TIMERS);
+    if constexpr (LB) {
+        OP_STAMP(10);
+        OP_NOTE(11, 100 + quick);
+    } else {
+        OP_CLOCK(7);                                                       // emission
+        OP_COUNT(11, 1);
+        OP_CLOCK_FLUSH();
+    }
+    if (k == nch - 1) {
+        fill_behind_cumsum(of, u_hi, Np, tid);
+        if (tid == 0 && a.status && u_hi < (int)Np) atomicOr(&a.status[f], ST_OVERRUN);
+    }
+}
+#undef OP_PHASE
+
 
 // TICKET = false (the default since round 3): chunk (f, k) is a function of blockIdx alone -- chunk-major over the filters --
 // instead of an atomic ticket.  A chunk only waits for chunks with a smaller blockIdx.  Forward progress: every hardware
@@ -789,47 +1305,13 @@ resample_onepass_kernel(const OpArgs a)
     if (f < 0) return;                                                     // cannot happen: one workgroup per chunk
     OP_CLOCK(0);                                                           // ticket
 
-    const double *wf = a.w + (long)f * Np;
-    int32_t *of = a.idx + (long)f * Np;
-    const double u_sys = STRATIFIED ? 0.0 : a.u[f];
-    const double *u_str = STRATIFIED ? a.u + (long)f * Np : nullptr;
-    const double Nd = (double)Np, halfNd = 0.5 * Nd;
+    const ChunkCtx<STRATIFIED> cx = chunk_ctx<STRATIFIED>(a, f, k);
     OpDesc *d = a.desc + (long)f * nch;
-    unsigned *abort_word = &a.ctl->abort;
-    const long base = (long)k * OP_TILE;
-    const int len = (int)((Np - base) < OP_TILE ? (Np - base) : OP_TILE);
 
-    // ---- weights: every thread reads its eight CONSECUTIVE weights straight from HBM (a wave covers 4 KiB with four
-    // 16-byte loads per lane: every byte of every line is used, nothing is staged or transposed through LDS) ----
     double w8[OP_ITEMS];
-    {
-        const double *src = wf + base + tid * OP_ITEMS;
-        if (len == OP_TILE && (((uintptr_t)(wf + base)) & 15) == 0) {                          // uniform
-            FK_UNROLL for (int q = 0; q < OP_ITEMS; q += 2) {
-                const f64x2 t = *reinterpret_cast<const f64x2 *>(src + q);
-                w8[q] = t.x;
-                w8[q + 1] = t.y;
-            }
-        } else if (len == OP_TILE) {
-            FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) w8[q] = src[q];
-        } else {
-            FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-                const int j = tid * OP_ITEMS + q;
-                const double t = wf[base + (j < len ? j : 0)];
-                w8[q] = j < len ? t : 0.0;
-            }
-        }
-    }
-    double s = 0.0, mn = 0.0;
-    FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-        s += w8[q];
-        mn = w8[q] < mn ? w8[q] : mn;                                      // a negative weight (NaN / Inf show in the sum)
-    }
-    s = lane_bcast(wave_incl_sum(s), 63);
-    if (lane == 0) sh.wsum[wave] = s;
-    const int any_neg = __syncthreads_or(mn < 0.0 ? 1 : 0);                                  // (A)
-    double S = (sh.wsum[0] + sh.wsum[1]) + (sh.wsum[2] + sh.wsum[3]);
-    const bool any_bad = any_neg || !(S < 0x1p1000);                       // negative, NaN, Inf or absurdly large
+    load_chunk(w8, a.w + (long)f * Np, (long)k * OP_TILE, Np, tid);
+    bool any_bad;
+    double S = chunk_sum(w8, sh.wsum, lane, wave, any_bad);                                   // (A)
     if (any_bad) S = __builtin_nan("");
     OP_CLOCK(1);                                                           // weights landed
 
@@ -858,13 +1340,7 @@ resample_onepass_kernel(const OpArgs a)
             bool tie0 = false, tie1 = single;
             double run0 = 0.0, run1 = 0.0;
             if (single) {
-                FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-                    const double x0 = scale2(w8[q], -g) + 0.5;
-                    const double i0 = floor(x0);
-                    tie0 = tie0 || (i0 == x0);
-                    run0 += i0;
-                    E[q] = run0;
-                }
+                run0 = thread_increments(w8, g, E, tie0);
             } else {
                 FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
                     const double t0 = scale2(w8[q], -g);
@@ -915,7 +1391,7 @@ resample_onepass_kernel(const OpArgs a)
                         publish_carry(&d[k], scale2(Cout, e));
                         st_agent(&d[k].approx, pack_approx(c_in + S, 2));  // what a successor on the two-stage path looks for
                     }
-                    out_lo = n_boundary_fast<STRATIFIED>(c_in, (int)Np, Nd, halfNd, u_sys, u_str);
+                    out_lo = chunk_boundary(c_in, cx);
                 }
                 if (lane == 0) {
                     sh.bc_d[1] = c_in;
@@ -931,11 +1407,8 @@ resample_onepass_kernel(const OpArgs a)
                 eu = g + which;
                 I = which ? I1 : I0;
                 if (which == 1) {                                          // the thread's inclusive sums at the other ulp
-                    double run = 0.0;
-                    FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-                        run += floor(scale2(w8[q], -eu) + 0.5);
-                        E[q] = run;
-                    }
+                    bool tie = false;                                      // (v1 above: there is none)
+                    const double run = thread_increments(w8, eu, E, tie);
                     const double winc = wave_incl_sum(run);
                     __syncthreads();                                       // (everybody has read wsum above)
                     if (lane == 63) sh.wsum[wave] = winc;
@@ -948,291 +1421,15 @@ resample_onepass_kernel(const OpArgs a)
             OP_CLOCK(2);                                                   // (speculation: counted as stage 1)
         }
     }
-    bool at_start = false;
-    if (!hit) {
-    // ---- stage 1: approximate carry-in --------------------------------------------------------------------
-    if (wave == 0) {
-        double A = 0.0;
-        if (k > 0) {
-            if (lane == 0) st_agent(&d[k].approx, pack_approx(S, 1));
-            A = lookback_approx(d, k, lane, abort_word);
-        }
-        if (lane == 0) {
-            st_agent(&d[k].approx, pack_approx(A + S, 2));
-            sh.bc_d[0] = A;
-        }
-    }
-    __syncthreads();                                                                          // (B)
-    const double A = sh.bc_d[0];
-    OP_CLOCK(2);                                                           // stage 1
-
-    // ---- what stage 1 tells this chunk --------------------------------------------------------------------
-    const bool poison = !(A >= 0.0 && S >= 0.0 && A + S < 0x1p1000);
-    if (poison) {                                                          // uniform
-        // a weight this path does not take (negative, NaN, huge) here or upstream: the whole filter is redone by
-        // resample_literal_kernel; successors only need to learn that quickly
-        if (tid == 0) {
-            publish_carry(&d[k], __builtin_nan(""));
-            if (any_bad) __hip_atomic_store(&a.bad[f], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (a.status && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                atomicOr(&a.status[f], ST_INTERNAL);
-        }
-        return;
-    }
-    // A == 0 means EXACTLY: every weight before this chunk is +0.0 (they are all >= 0), so the carry-in is 0 and
-    // needs no stage 2; with S == 0 as well the chunk is empty-handed: carry-out 0, no slots
-    at_start = (k == 0) || (A == 0.0);
-    bool clean = false;
-    {
-        const double lo = A * (1.0 - a.delta), hi = (A + S) * (1.0 + a.delta);
-        if (lo > OP_SANE_LO && hi < OP_SANE_HI && ulp_exp(lo) == ulp_exp(hi)) {
-            clean = true;
-            eu = ulp_exp(lo);
-        }
-    }
-    // increments in the promised binade (fk_exact_scan.hpp, fast_inc): inc = floor(w / ulp + 1/2) unless the
-    // remainder is exactly half an ulp -- such a chunk, and one whose sums reach 2^53 (which is also where t + 1/2
-    // stops being exact, and then the test fires by itself), leaves this path.  E[q] = inclusive sums of the thread.
-    excl = 0.0;
-    I = 0.0;
-    bool fast = false;
-    if (clean) {                                                           // uniform
-        bool tie = false;
-        double run = 0.0;
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-            const double x = scale2(w8[q], -eu) + 0.5;
-            const double i = floor(x);
-            tie = tie || (i == x);
-            run += i;
-            E[q] = run;
-        }
-        const double winc = wave_incl_sum(run);
-        if (lane == 63) sh.wsum[wave] = winc;
-        const int any_tie = __syncthreads_or(tie ? 1 : 0);                                    // (C)
-        excl = winc - run;                                                 // exact: everything is an integer < 2^53 ...
-        FK_UNROLL for (int wv = 0; wv < OP_THREADS / 64; ++wv) {
-            if (wv < wave) excl += sh.wsum[wv];
-            I += sh.wsum[wv];
-        }
-        fast = !any_tie && I < 0x1p53;                                     // ... or this says so
-    } else {
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) E[q] = 0.0;
-    }
-    OP_CLOCK(3);                                                           // increments
-
-    // ---- stage 2: exact carry-in ---------------------------------------------------------------------------
-    if (wave == 0) {
-        double c_in = 0.0;
-        bool ok = true;
-        if (!at_start) {
-            if (fast && lane == 0) st_agent(&d[k].exact, pack_exact(1, eu, I));
-            c_in = lookback_exact(d, k, fast, eu, lane, abort_word, ok);
-        }
-        // carry-out of a chunk that stayed inside its binade: known right now, successors need not wait for the scan
-        int quick = 0;
-        if (ok && fast && c_in > OP_SANE_LO && c_in < OP_SANE_HI && ulp_exp(c_in) == eu) {
-            const double Cout = scale2(c_in, -eu) + I;
-            if (Cout < 0x1p53) {
-                quick = 1;
-                if (lane == 0) publish_carry(&d[k], scale2(Cout, eu));
-            }
-        }
-        if (ok && at_start && S == 0.0) {
-            quick = 2;                                                     // still nothing but zeros
-            if (lane == 0) publish_carry(&d[k], 0.0);
-        }
-        // first slot of this chunk: everything below n(carry-in) belongs to earlier chunks
-        const int out_lo = at_start ? 0 : n_boundary_fast<STRATIFIED>(c_in, (int)Np, Nd, halfNd, u_sys, u_str);
-        if (lane == 0) {
-            sh.bc_d[1] = c_in;
-            sh.bc_i[3] = ok ? quick : -1;
-            sh.bc_i[4] = out_lo;
-        }
-    }
-    __syncthreads();                                                                          // (D)
-    }   // !hit
-    const double c_in = sh.bc_d[1];
-    const int quick = __builtin_amdgcn_readfirstlane(sh.bc_i[3]);
-    const int u_lo = __builtin_amdgcn_readfirstlane(sh.bc_i[4]);
-    OP_CLOCK(4);                                                           // stage 2
-    OP_COUNT(8 + (quick < 0 ? 3 : quick), 1);                              // 8: general, 9: quick, 10: zeros
-    if (quick < 0) {                                                       // abort: a predecessor never published
-        if (tid == 0 && a.status) atomicOr(&a.status[f], ST_INTERNAL);
-        return;
-    }
-
-    // ---- slot boundaries: weight j owns the slots [n_{j-1}, n_j), n_j = n(cs_j)  (fk_resample_math.hpp) -----------
-    int nb[OP_ITEMS];
-    bool win_ready = true;
-    if (quick == 1) {                                                      // uniform
-        // cs_j = (C0 + E_j) ulp exactly, so N cs_j - u = fma(E_j, N ulp, C0 N ulp - u): ONE fma per weight gives the
-        // estimate whose ceiling is n_j whenever it is not within eps of an integer (n_boundary_fast's argument:
-        // here two roundings of 2^-22 slots each, the same budget); the rare rest takes the exact tests on cs_j.
-        const double ulp = scale2(1.0, eu), C0 = scale2(c_in, -eu), Nu = scale2(Nd, eu);
-        const double K = __builtin_fma(C0, Nu, STRATIFIED ? 0.0 : -u_sys);
-        unsigned unsure = 0;
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-            const double Et = excl + E[q];                                 // exact
-            const double e = __builtin_fma(Et, Nu, K);
-            // floor(e) + 1 without a v_floor_f64 / v_cvt_i32_f64 pair: m = e + 1.5 2^52 holds the nearest integer
-            // of e in its low mantissa bits (two's complement; -1 < e < Nd < 2^31 where the result is used), dd = e - nearest
-            const double m = e + 0x1.8p52;
-            const double dd = e - (m - 0x1.8p52);                          // exact, |dd| <= 1/2
-            const int ri = (int)(unsigned)double_to_bits(m);
-            bool sure = fabs(dd) > N_BOUNDARY_EPS && e < Nd;               // (= fr in (eps, 1 - eps))
-            int n = ri + (dd < 0.0 ? 0 : 1);
-            if (STRATIFIED) {
-                const int fl = ri - (dd < 0.0 ? 1 : 0);
-                const double fr = dd < 0.0 ? dd + 1.0 : dd;                // e - floor(e), exact
-                const double uf = u_str[e < Nd ? fl : 0];                  // e >= 0 here
-                const double gap = uf - fr;
-                sure = sure && (gap > N_BOUNDARY_EPS || gap < -N_BOUNDARY_EPS);
-                n = fl + (gap > 0.0 ? 0 : 1);
-            }
-            unsure |= sure ? 0u : (1u << q);
-            nb[q] = n;
-        }
-        if (unsure) {                                                      // about one weight in 10^5: the exact tests
-            // ONE inlined copy in a rolled loop; E[q] / nb[q] are picked and put back with selects (registers
-            // cannot be indexed)
-            _Pragma("nounroll") for (int q = 0; q < OP_ITEMS; ++q) {
-                if (!(unsure & (1u << q))) continue;
-                double Eq = E[0];
-                FK_UNROLL for (int r = 1; r < OP_ITEMS; ++r) Eq = (q == r) ? E[r] : Eq;
-                const int n = n_boundary<STRATIFIED>((C0 + (excl + Eq)) * ulp, (int)Np, Nd, halfNd, u_sys, u_str);
-                FK_UNROLL for (int r = 0; r < OP_ITEMS; ++r) nb[r] = (q == r) ? n : nb[r];
-            }
-        }
-#ifdef FK_OP_CLOCKS
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-            if (g_dbg_cs && tid * OP_ITEMS + q < len) {
-                g_dbg_cs[(long)f * Np + base + tid * OP_ITEMS + q] = (C0 + (excl + E[q])) * ulp;
-                g_dbg_n[(long)f * Np + base + tid * OP_ITEMS + q] = nb[q];
-            }
-        }
-#endif
-        OP_CLOCK(5);
-    } else if (quick == 2) {
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) nb[q] = 0;
-        OP_CLOCK(5);
-    } else {
-        // general scan: the weights once more (L2), now into the padded LDS tile the scan works in
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-            const int j = tid * OP_ITEMS + q;
-            sh.tile[pad8(j)] = j < len ? wf[base + j] : 0.0;
-        }
-        __syncthreads();
-        const double c_out = general_cumsum(sh, len, c_in);
-        if (tid == 0) publish_carry(&d[k], c_out);
-        OP_CLOCK(5);                                                       // general scan
-        // (each thread reads back only its own slots, behind general_cumsum's final barrier; n_j goes into the low
-        // half of cs_j's slot so that this loop stays rolled)
-        int *nslot = reinterpret_cast<int *>(&sh.tile[pad8(tid * OP_ITEMS)]);
-        _Pragma("nounroll") for (int q = 0; q < OP_ITEMS; ++q) {
-            const int j = tid * OP_ITEMS + q;
-            const double c = j < len ? sh.tile[pad8(j)] : c_out;
-            const int n = n_boundary_fast<STRATIFIED>(c, (int)Np, Nd, halfNd, u_sys, u_str);
-            nslot[2 * q] = n;
-#ifdef FK_OP_CLOCKS
-            if (g_dbg_cs && j < len) {
-                g_dbg_cs[(long)f * Np + base + j] = c;
-                g_dbg_n[(long)f * Np + base + j] = n;
-            }
-#endif
-        }
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) nb[q] = nslot[2 * q];
-        win_ready = false;                                                 // the tile overwrote the window
-    }
-    sh.nlast[tid] = nb[OP_ITEMS - 1];
-    __syncthreads();                                                                          // (E)
-    int nprev = tid == 0 ? u_lo : sh.nlast[tid - 1];
-    const int u_hi = __builtin_amdgcn_readfirstlane(sh.nlast[OP_THREADS - 1]);
-    // heads: the slot where each non-empty run starts (boundaries are non-decreasing for valid input)
-    int head[OP_ITEMS];
-    FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-        head[q] = nb[q] > nprev ? nprev : -1;
-        nprev = nb[q] > nprev ? nb[q] : nprev;
-    }
-    OP_CLOCK(6);                                                           // boundaries
-
-    // ---- emission: windows of OP_WIN slots; heads -> inclusive max-scan -> coalesced 16-byte stores --------------
-    // (slot numbers fit an int: Np < 2^31; everything about a window is wave-uniform and lives in SGPRs)
-    const int mis = (int)(((uintptr_t)of >> 2) & 3);
-    int seed = -1;
-    for (int wb = u_lo - ((mis + u_lo) & 3); u_hi > u_lo && wb < u_hi; wb += OP_WIN) {        // uniform
-        if (!win_ready) {
-            __syncthreads();                                               // everybody is done with the tile / the last window
-            init_window(win, tid);
-            __syncthreads();
-        }
-        win_ready = false;
-        int have = 0;
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-            const unsigned h = (unsigned)(head[q] - wb);                   // a head below wb wraps to a huge number
-            if (head[q] >= 0 && h < (unsigned)OP_WIN) {
-                win[h] = (int)base + tid * OP_ITEMS + q;
-                have = 1;
-            }
-        }
-        const int any_head = __syncthreads_or(have);                                          // (G)
-        const int lim = u_hi - wb;                                         // slots [max(first, 0), lim) are ours
-        const int first = u_lo - wb;
-        int32_t *ow = of + wb;                                             // uniform; 16-byte aligned
-        const int s0 = 12 * tid;
-        int x[12];
-        if (any_head) {                                                    // uniform
-            FK_UNROLL for (int g = 0; g < 3; ++g) {
-                const i32x4 t = *reinterpret_cast<const i32x4 *>(&win[s0 + 4 * g]);
-                x[4 * g + 0] = t.x;
-                x[4 * g + 1] = t.y;
-                x[4 * g + 2] = t.z;
-                x[4 * g + 3] = t.w;
-            }
-            FK_UNROLL for (int e = 1; e < 12; ++e) x[e] = x[e] > x[e - 1] ? x[e] : x[e - 1];
-            const int wincl = wave_incl_max(x[11]);
-            if (lane == 63) sh.wmax[wave] = wincl;
-            __syncthreads();
-            const int up = __shfl_up(wincl, 1, 64);
-            int pre = (lane == 0 || up < seed) ? seed : up;               // everything before this thread, this wave
-            FK_UNROLL for (int wv = 0; wv < OP_THREADS / 64; ++wv) {
-                const int t = sh.wmax[wv];
-                if (wv < wave) pre = pre > t ? pre : t;
-                seed = seed > t ? seed : t;                                // every thread: running max after this window
-            }
-            FK_UNROLL for (int e = 0; e < 12; ++e) x[e] = x[e] > pre ? x[e] : pre;
-        } else {
-            // the whole window lies inside one run (a weight owning more than OP_WIN slots): constant fill
-            FK_UNROLL for (int e = 0; e < 12; ++e) x[e] = seed;
-        }
-        if (s0 < lim) {
-            FK_UNROLL for (int g = 0; g < 3; ++g) {
-                const int sg = s0 + 4 * g;
-                if (sg >= first && sg + 3 < lim) *reinterpret_cast<i32x4 *>(&ow[sg]) = i32x4{x[4 * g], x[4 * g + 1], x[4 * g + 2], x[4 * g + 3]};
-                else {
-                    FK_UNROLL for (int e = 0; e < 4; ++e)
-                        if (sg + e >= first && sg + e < lim) ow[sg + e] = x[4 * g + e];
-                }
-            }
-        }
-    }
-    OP_CLOCK(7);                                                           // emission
-    OP_COUNT(11, 1);
-    OP_CLOCK_FLUSH();
-
-    // ---- end of the vector: positions >= cumsum[-1] (the reference raises IndexError, resampling.py:109,145) --
-    if (k == nch - 1) {
-        for (long i = (long)u_hi + tid; i < Np; i += OP_THREADS) of[i] = (int32_t)(Np - 1);
-        if (tid == 0 && a.status && u_hi < (int)Np) atomicOr(&a.status[f], ST_OVERRUN);
-    }
+    // ---- the chunk itself: both stages unless the speculation has hit, boundaries, emission, end of the vector ----
+    op_resolve_chunk<STRATIFIED, false>(sh, a, cx, f, k, w8, S, any_bad, hit, E, excl, I, eu, 0 OP_TIMERS);
 }
 
 #include "resample_onepass2.inc"
 
-// ---- the chunk as round 3's kernel resolves it when the speculation does not apply: stage 1 -> stage 2 -> boundaries (quick /
-// zeros / general scan) -> emission -> end of the vector.  A verbatim copy of resample_onepass_kernel's body from "stage 1" on
-// (that kernel stays as it is: FK_OP_V2=0 is the A/B), out of line: resample_onepass2_kernel calls it for the chunks its fast
-// path declines -- a miss of the guess, a tie, the start of a vector, the last chunk, garbage -- so that those never cost the
-// fast path a register.  The eight weights are read again (L2); everything else is recomputed from them.
+// ---- the chunks resample_onepass2_kernel's fast path declines -- a miss of the guess, a tie, the start of a vector, the last
+// chunk, garbage: op_resolve_chunk with round 6's additions, behind one call site so that those never cost the fast path a
+// register.  The eight weights are read again (L2); everything else is recomputed from them.
 template <bool STRATIFIED, int BUDGET>
 __device__ OP2_SLOW_INLINE void op_chunk_slow(OpShared &sh, const double *a_w, const double *a_u, int32_t *a_idx, int32_t *a_status,
                                                         OpCtl *a_ctl, OpDesc *a_desc, int *a_bad, const double a_delta, const long a_Np,
@@ -1243,16 +1440,11 @@ __device__ OP2_SLOW_INLINE void op_chunk_slow(OpShared &sh, const double *a_w, c
     OpArgs a = {};
     a.w = a_w; a.u = a_u; a.idx = a_idx; a.status = a_status; a.ctl = a_ctl; a.desc = a_desc; a.bad = a_bad;
     a.delta = a_delta; a.Np = a_Np; a.nch = a_nch;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long Np = a.Np, nch = a.nch;
-    int *win = sh.win();
+    const int tid = threadIdx.x;
+    const long Np = a.Np;
+    [[maybe_unused]] const long nch = a.nch;                               // (OP_STAMP)
     const double *wf = a.w + (long)f * Np;
-    int32_t *of = a.idx + (long)f * Np;
-    const double u_sys = STRATIFIED ? 0.0 : a.u[f];
-    const double *u_str = STRATIFIED ? a.u + (long)f * Np : nullptr;
-    const double Nd = (double)Np, halfNd = 0.5 * Nd;
-    OpDesc *d = a.desc + (long)f * nch;
-    unsigned *abort_word = &a.ctl->abort;
+    const ChunkCtx<STRATIFIED> cx = chunk_ctx<STRATIFIED>(a, f, k);
     const long base = (long)k * OP_TILE;
     const int len = (int)((Np - base) < OP_TILE ? (Np - base) : OP_TILE);
     // (the weights once more, from L2.  Handing the caller's registers over -- the path is inlined -- was tried: the allocator then
@@ -1263,341 +1455,16 @@ __device__ OP2_SLOW_INLINE void op_chunk_slow(OpShared &sh, const double *a_w, c
         const double t = wf[base + (j < len ? j : 0)];
         w8[q] = j < len ? t : 0.0;
     }
-    // (lb_mode & 8: 64 predecessors per look-back step instead of 16 -- calls with few long vectors walk hundreds of chunks back.
-    //  Measured with and without, and with s_setprio 3 on this path: 1 x 8e6 108 / 110 / 111 us, nothing -- profiles/r06/onepass/r06o)
-    const int lbw = (lb_mode & 8) ? 64 : OP_LB;
     const bool any_bad = any_bad_in != 0;
     const double S = any_bad ? __builtin_nan("") : S_in;
     double E[OP_ITEMS];
     double excl = 0.0, I = 0.0;
     int eu = 0;
-    const bool hit = false;
     __syncthreads();                                                       // everybody has left the fast path's LDS slots
     OP_STAMP(5);
-    init_window(win, tid);
-    bool at_start = false;
-    SegRegs R;
-    bool prepared = false, scan_tried = false;
-    if (!hit) {
-    // ---- stage 1: approximate carry-in --------------------------------------------------------------------
-    if (wave == 0) {
-        double A = 0.0;
-        if (k > 0) {
-            if (lane == 0) st_agent(&d[k].approx, pack_approx(S, 1));
-            A = lookback_approx(d, k, lane, abort_word, lbw);
-        }
-        if (lane == 0) {
-            st_agent(&d[k].approx, pack_approx(A + S, 2));
-            sh.bc_d[0] = A;
-        }
-    }
-    __syncthreads();                                                                          // (B)
-    OP_STAMP(6);
-    const double A = sh.bc_d[0];
-
-    // ---- what stage 1 tells this chunk --------------------------------------------------------------------
-    const bool poison = !(A >= 0.0 && S >= 0.0 && A + S < 0x1p1000);
-    if (poison) {                                                          // uniform
-        // a weight this path does not take (negative, NaN, huge) here or upstream: the whole filter is redone by
-        // resample_literal_kernel; successors only need to learn that quickly
-        if (tid == 0) {
-            publish_carry(&d[k], __builtin_nan(""));
-            if (any_bad) __hip_atomic_store(&a.bad[f], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (a.status && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                atomicOr(&a.status[f], ST_INTERNAL);
-        }
-        return;
-    }
-    // A == 0 means EXACTLY: every weight before this chunk is +0.0 (they are all >= 0), so the carry-in is 0 and
-    // needs no stage 2; with S == 0 as well the chunk is empty-handed: carry-out 0, no slots
-    at_start = (k == 0) || (A == 0.0);
-    bool clean = false;
-    {
-        const double lo = A * (1.0 - a.delta), hi = (A + S) * (1.0 + a.delta);
-        if (lo > OP_SANE_LO && hi < OP_SANE_HI && ulp_exp(lo) == ulp_exp(hi)) {
-            clean = true;
-            eu = ulp_exp(lo);
-        }
-    }
-    // increments in the promised binade (fk_exact_scan.hpp, fast_inc): inc = floor(w / ulp + 1/2) unless the
-    // remainder is exactly half an ulp -- such a chunk, and one whose sums reach 2^53 (which is also where t + 1/2
-    // stops being exact, and then the test fires by itself), leaves this path.  E[q] = inclusive sums of the thread.
-    excl = 0.0;
-    I = 0.0;
-    bool fast = false;
-    if (clean) {                                                           // uniform
-        bool tie = false;
-        double run = 0.0;
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-            const double x = scale2(w8[q], -eu) + 0.5;
-            const double i = floor(x);
-            tie = tie || (i == x);
-            run += i;
-            E[q] = run;
-        }
-        const double winc = wave_incl_sum(run);
-        if (lane == 63) sh.wsum[wave] = winc;
-        const int any_tie = __syncthreads_or(tie ? 1 : 0);                                    // (C)
-        excl = winc - run;                                                 // exact: everything is an integer < 2^53 ...
-        FK_UNROLL for (int wv = 0; wv < OP_THREADS / 64; ++wv) {
-            if (wv < wave) excl += sh.wsum[wv];
-            I += sh.wsum[wv];
-        }
-        fast = !any_tie && I < 0x1p53;                                     // ... or this says so
-    } else {
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) E[q] = 0.0;
-    }
-
-    // ---- a chunk that needs the general scan prepares it NOW (lb_mode & 4): the weights into the tile, seg_prepare on the
-    // APPROXIMATE carry-in of stage 1 (relative error <= a.delta; exactly 0 at the start of a vector) -- all of this before the
-    // exact carry-in has arrived, while the chunks below are still being resolved.  What is left behind the carry is
-    // seg_chain, a few dependent adds by wave 0, and the carry-out goes out at once: with few long vectors every crossing of
-    // a binade and every tie-holder sits on the one chain all later chunks wait for, and it used to hold that chain for a
-    // reload of its weights, five barriers and the whole scan -- 7 us per crossing, 19 crossings in a row at 1 x 2e6
-    // (tools/op_timeline.py; profiles/r06/onepass/timeline_before.txt).
-    if (!fast && (lb_mode & 4) && !(at_start && S == 0.0)) {               // uniform
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) sh.tile[pad8(tid * OP_ITEMS + q)] = w8[q];   // (0.0 behind len)
-        __syncthreads();
-        scan_tried = true;
-        prepared = seg_prepare<true>(sh, len, at_start ? 0.0 : A, (at_start ? 0.0 : a.delta) + 0x1p-38, R);
-#ifdef FK_OP_CLOCKS
-        {   // (tools/op_timeline.py: core clocks / 16 between the barriers of seg_prepare, 16 bits each)
-            const SegShared &sg = sh.seg;
-            auto d16 = [](long long d) -> unsigned long long { d >>= 4; return (unsigned long long)(d < 0 ? 0 : (d > 65535 ? 65535 : d)); };
-            OP_NOTE(2, d16(sg.dbg_t[0] - sg.dbg_in) | (d16(sg.dbg_t[1] - sg.dbg_t[0]) << 16) | (d16(sg.dbg_t[2] - sg.dbg_t[1]) << 32) | (d16(sg.dbg_t[3] - sg.dbg_t[2]) << 48));
-        }
-#endif
-    }
-    // ---- stage 2: exact carry-in ---------------------------------------------------------------------------
-    OP_STAMP(7);
-    if (wave == 0) {
-        double c_in = 0.0;
-        bool ok = true;
-        if (!at_start) {
-            if (fast && lane == 0) st_agent(&d[k].exact, pack_exact(1, eu, I));
-            // (lb_mode & 2: a chunk that does NOT stay inside one binade -- a crossing -- still knows the binade of its carry-in from
-            //  stage 1, and may add up the predecessors' increment sums in THAT binade down to the nearest carry-out like anybody
-            //  else (the argument of lookback_exact is about the chunks in between, not about this one) instead of waiting for
-            //  chunk k-1 to see that carry, add the same sums and publish: one global round trip less per binade on the chain
-            //  every chunk of the binade above waits for)
-            bool lb_ok = fast;
-            int lb_eu = eu;
-            if (!fast && (lb_mode & 2)) {
-                const double lo = A * (1.0 - a.delta), hi = A * (1.0 + a.delta);
-                if (lo > OP_SANE_LO && hi < OP_SANE_HI && ulp_exp(lo) == ulp_exp(hi)) {
-                    lb_ok = true;
-                    lb_eu = ulp_exp(lo);
-                }
-            }
-            c_in = lookback_exact(d, k, lb_ok, lb_eu, lane, abort_word, ok, lbw);
-        }
-        // carry-out of a chunk that stayed inside its binade: known right now, successors need not wait for the scan
-        int quick = 0;
-        if (ok && fast && c_in > OP_SANE_LO && c_in < OP_SANE_HI && ulp_exp(c_in) == eu) {
-            const double Cout = scale2(c_in, -eu) + I;
-            if (Cout < 0x1p53) {
-                quick = 1;
-                if (lane == 0) publish_carry(&d[k], scale2(Cout, eu));
-            }
-        }
-        if (ok && at_start && S == 0.0) {
-            quick = 2;                                                     // still nothing but zeros
-            if (lane == 0) publish_carry(&d[k], 0.0);
-        }
-        if (ok && prepared && sh.seg.fail == 0) {                          // (behind seg_prepare's last barrier: every thread's verdict)
-            bool failed;
-            const double c_out = seg_chain(sh, c_in, R.D, R.ptotal, lane, failed);
-            if (!failed && lane == 0) publish_carry(&d[k], c_out);
-            OP_STAMP(14);
-        }
-        // first slot of this chunk: everything below n(carry-in) belongs to earlier chunks
-        const int out_lo = at_start ? 0 : n_boundary_fast<STRATIFIED>(c_in, (int)Np, Nd, halfNd, u_sys, u_str);
-        if (lane == 0) {
-            sh.bc_d[1] = c_in;
-            sh.bc_i[3] = ok ? quick : -1;
-            sh.bc_i[4] = out_lo;
-        }
-    }
-    __syncthreads();                                                                          // (D)
-    OP_STAMP(8);
-    }   // !hit
-    const double c_in = sh.bc_d[1];
-    const int quick = __builtin_amdgcn_readfirstlane(sh.bc_i[3]);
-    const int u_lo = __builtin_amdgcn_readfirstlane(sh.bc_i[4]);
-    if (quick < 0) {                                                       // abort: a predecessor never published
-        if (tid == 0 && a.status) atomicOr(&a.status[f], ST_INTERNAL);
-        return;
-    }
-
-    // ---- slot boundaries: weight j owns the slots [n_{j-1}, n_j), n_j = n(cs_j)  (fk_resample_math.hpp) -----------
-    int nb[OP_ITEMS];
-    bool win_ready = true;
-    if (quick == 1) {                                                      // uniform
-        // cs_j = (C0 + E_j) ulp exactly, so N cs_j - u = fma(E_j, N ulp, C0 N ulp - u): ONE fma per weight gives the
-        // estimate whose ceiling is n_j whenever it is not within eps of an integer (n_boundary_fast's argument:
-        // here two roundings of 2^-22 slots each, the same budget); the rare rest takes the exact tests on cs_j.
-        const double ulp = scale2(1.0, eu), C0 = scale2(c_in, -eu), Nu = scale2(Nd, eu);
-        const double K = __builtin_fma(C0, Nu, STRATIFIED ? 0.0 : -u_sys);
-        unsigned unsure = 0;
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-            const double Et = excl + E[q];                                 // exact
-            const double e = __builtin_fma(Et, Nu, K);
-            // floor(e) + 1 without a v_floor_f64 / v_cvt_i32_f64 pair: m = e + 1.5 2^52 holds the nearest integer
-            // of e in its low mantissa bits (two's complement; -1 < e < Nd < 2^31 where the result is used), dd = e - nearest
-            const double m = e + 0x1.8p52;
-            const double dd = e - (m - 0x1.8p52);                          // exact, |dd| <= 1/2
-            const int ri = (int)(unsigned)double_to_bits(m);
-            bool sure = fabs(dd) > N_BOUNDARY_EPS && e < Nd;               // (= fr in (eps, 1 - eps))
-            int n = ri + (dd < 0.0 ? 0 : 1);
-            if (STRATIFIED) {
-                const int fl = ri - (dd < 0.0 ? 1 : 0);
-                const double fr = dd < 0.0 ? dd + 1.0 : dd;                // e - floor(e), exact
-                const double uf = u_str[e < Nd ? fl : 0];                  // e >= 0 here
-                const double gap = uf - fr;
-                sure = sure && (gap > N_BOUNDARY_EPS || gap < -N_BOUNDARY_EPS);
-                n = fl + (gap > 0.0 ? 0 : 1);
-            }
-            unsure |= sure ? 0u : (1u << q);
-            nb[q] = n;
-        }
-        if (unsure) {                                                      // about one weight in 10^5: the exact tests
-            // ONE inlined copy in a rolled loop; E[q] / nb[q] are picked and put back with selects (registers
-            // cannot be indexed)
-            _Pragma("nounroll") for (int q = 0; q < OP_ITEMS; ++q) {
-                if (!(unsure & (1u << q))) continue;
-                double Eq = E[0];
-                FK_UNROLL for (int r = 1; r < OP_ITEMS; ++r) Eq = (q == r) ? E[r] : Eq;
-                const int n = n_boundary<STRATIFIED>((C0 + (excl + Eq)) * ulp, (int)Np, Nd, halfNd, u_sys, u_str);
-                FK_UNROLL for (int r = 0; r < OP_ITEMS; ++r) nb[r] = (q == r) ? n : nb[r];
-            }
-        }
-#ifdef FK_OP_CLOCKS
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-            if (g_dbg_cs && tid * OP_ITEMS + q < len) {
-                g_dbg_cs[(long)f * Np + base + tid * OP_ITEMS + q] = (C0 + (excl + E[q])) * ulp;
-                g_dbg_n[(long)f * Np + base + tid * OP_ITEMS + q] = nb[q];
-            }
-        }
-#endif
-    } else if (quick == 2) {
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) nb[q] = 0;
-    } else {
-        double c_out = 0.0;
-        if (prepared && sh.seg.fail == 0) {                                // uniform (behind barrier (D))
-            seg_finish(sh, len, R);
-            c_out = sh.seg.carry_out;                                      // (published by wave 0 the moment it was known)
-        } else {
-            // general scan: the weights into the padded LDS tile the scan works in (a prepared scan that declined left them there)
-            if (!prepared) {
-                __syncthreads();
-                FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) sh.tile[pad8(tid * OP_ITEMS + q)] = w8[q];
-            }
-            __syncthreads();
-            // (round 6: the one-round scan first -- binades predicted for all elements at once, then verified; round 3 went straight
-            //  to general_cumsum, one block scan and four barriers per binade the running sum passes through: ~45 k clocks for the
-            //  first chunk of a vector, ~20 k for a crossing)
-            if (scan_tried || !segmented_cumsum(sh, len, c_in, &c_out)) c_out = general_cumsum(sh, len, c_in);
-            if (tid == 0) publish_carry(&d[k], c_out);
-        }
-        OP_STAMP(9);
-        OP_NOTE(15, (prepared ? 1 : 0) | (sh.seg.fail ? 2 : 0) | ((unsigned)R.D << 8));
-        // (each thread reads back only its own slots, behind general_cumsum's final barrier; n_j goes into the low
-        // half of cs_j's slot so that this loop stays rolled)
-        int *nslot = reinterpret_cast<int *>(&sh.tile[pad8(tid * OP_ITEMS)]);
-        _Pragma("nounroll") for (int q = 0; q < OP_ITEMS; ++q) {
-            const int j = tid * OP_ITEMS + q;
-            const double c = j < len ? sh.tile[pad8(j)] : c_out;
-            const int n = n_boundary_fast<STRATIFIED>(c, (int)Np, Nd, halfNd, u_sys, u_str);
-            nslot[2 * q] = n;
-#ifdef FK_OP_CLOCKS
-            if (g_dbg_cs && j < len) {
-                g_dbg_cs[(long)f * Np + base + j] = c;
-                g_dbg_n[(long)f * Np + base + j] = n;
-            }
-#endif
-        }
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) nb[q] = nslot[2 * q];
-        win_ready = false;                                                 // the tile overwrote the window
-    }
-    sh.nlast[tid] = nb[OP_ITEMS - 1];
-    __syncthreads();                                                                          // (E)
-    int nprev = tid == 0 ? u_lo : sh.nlast[tid - 1];
-    const int u_hi = __builtin_amdgcn_readfirstlane(sh.nlast[OP_THREADS - 1]);
-    // heads: the slot where each non-empty run starts (boundaries are non-decreasing for valid input)
-    int head[OP_ITEMS];
-    FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-        head[q] = nb[q] > nprev ? nprev : -1;
-        nprev = nb[q] > nprev ? nb[q] : nprev;
-    }
-
-    // ---- emission: windows of OP_WIN slots; heads -> inclusive max-scan -> coalesced 16-byte stores --------------
-    // (slot numbers fit an int: Np < 2^31; everything about a window is wave-uniform and lives in SGPRs)
-    const int mis = (int)(((uintptr_t)of >> 2) & 3);
-    int seed = -1;
-    for (int wb = u_lo - ((mis + u_lo) & 3); u_hi > u_lo && wb < u_hi; wb += OP_WIN) {        // uniform
-        if (!win_ready) {
-            __syncthreads();                                               // everybody is done with the tile / the last window
-            init_window(win, tid);
-            __syncthreads();
-        }
-        win_ready = false;
-        int have = 0;
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-            const unsigned h = (unsigned)(head[q] - wb);                   // a head below wb wraps to a huge number
-            if (head[q] >= 0 && h < (unsigned)OP_WIN) {
-                win[h] = (int)base + tid * OP_ITEMS + q;
-                have = 1;
-            }
-        }
-        const int any_head = __syncthreads_or(have);                                          // (G)
-        const int lim = u_hi - wb;                                         // slots [max(first, 0), lim) are ours
-        const int first = u_lo - wb;
-        int32_t *ow = of + wb;                                             // uniform; 16-byte aligned
-        const int s0 = 12 * tid;
-        int x[12];
-        if (any_head) {                                                    // uniform
-            FK_UNROLL for (int g = 0; g < 3; ++g) {
-                const i32x4 t = *reinterpret_cast<const i32x4 *>(&win[s0 + 4 * g]);
-                x[4 * g + 0] = t.x;
-                x[4 * g + 1] = t.y;
-                x[4 * g + 2] = t.z;
-                x[4 * g + 3] = t.w;
-            }
-            FK_UNROLL for (int e = 1; e < 12; ++e) x[e] = x[e] > x[e - 1] ? x[e] : x[e - 1];
-            const int wincl = wave_incl_max(x[11]);
-            if (lane == 63) sh.wmax[wave] = wincl;
-            __syncthreads();
-            const int up = __shfl_up(wincl, 1, 64);
-            int pre = (lane == 0 || up < seed) ? seed : up;               // everything before this thread, this wave
-            FK_UNROLL for (int wv = 0; wv < OP_THREADS / 64; ++wv) {
-                const int t = sh.wmax[wv];
-                if (wv < wave) pre = pre > t ? pre : t;
-                seed = seed > t ? seed : t;                                // every thread: running max after this window
-            }
-            FK_UNROLL for (int e = 0; e < 12; ++e) x[e] = x[e] > pre ? x[e] : pre;
-        } else {
-            // the whole window lies inside one run (a weight owning more than OP_WIN slots): constant fill
-            FK_UNROLL for (int e = 0; e < 12; ++e) x[e] = seed;
-        }
-        if (s0 < lim) {
-            FK_UNROLL for (int g = 0; g < 3; ++g) {
-                const int sg = s0 + 4 * g;
-                if (sg >= first && sg + 3 < lim) *reinterpret_cast<i32x4 *>(&ow[sg]) = i32x4{x[4 * g], x[4 * g + 1], x[4 * g + 2], x[4 * g + 3]};
-                else {
-                    FK_UNROLL for (int e = 0; e < 4; ++e)
-                        if (sg + e >= first && sg + e < lim) ow[sg + e] = x[4 * g + e];
-                }
-            }
-        }
-    }
-
-    OP_STAMP(10);
-    OP_NOTE(11, 100 + quick);
-    // ---- end of the vector: positions >= cumsum[-1] (the reference raises IndexError, resampling.py:109,145) --
-    if (k == nch - 1) {
-        for (long i = (long)u_hi + tid; i < Np; i += OP_THREADS) of[i] = (int32_t)(Np - 1);
-        if (tid == 0 && a.status && u_hi < (int)Np) atomicOr(&a.status[f], ST_OVERRUN);
-    }
+    init_window(sh.win(), tid);
+    OP_UNTIMED();
+    op_resolve_chunk<STRATIFIED, true>(sh, a, cx, f, k, w8, S, any_bad, false, E, excl, I, eu, lb_mode OP_TIMERS);
 }
 
 // ---- short vectors: one workgroup per filter, its chunks in sequence, the carry in a register ------------------------
@@ -1607,160 +1474,7 @@ __device__ OP2_SLOW_INLINE void op_chunk_slow(OpShared &sh, const double *a_w, c
 // round general_cumsum.  Before: one
 // workgroup per filter walking 2048-weight tiles with an int64 Mono scan per binade and one binary search per output
 // slot, 140 us for 1000 x 8000.)
-template <bool STRATIFIED>
-struct ChunkCtx {
-    long Np;
-    double Nd, halfNd, u_sys;
-    const double *u_str;
-};
-
-// slot boundaries of a chunk that stayed inside the binade of its carry-in: cs_j = (C0 + excl + E_j) 2^eu
-template <bool STRATIFIED>
-__device__ __forceinline__ void quick_boundaries(const double (&E)[OP_ITEMS], double excl, double c_in, int eu,
-                                                 const ChunkCtx<STRATIFIED> &cx, int (&nb)[OP_ITEMS])
-{
-    const double ulp = scale2(1.0, eu), C0 = scale2(c_in, -eu), Nu = scale2(cx.Nd, eu);
-    const double K = __builtin_fma(C0, Nu, STRATIFIED ? 0.0 : -cx.u_sys);
-    unsigned unsure = 0;
-    FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-        const double Et = excl + E[q];                                     // exact
-        const double e = __builtin_fma(Et, Nu, K);
-        const double m = e + 0x1.8p52;                                     // (as in resample_onepass_kernel)
-        const double dd = e - (m - 0x1.8p52);
-        const int ri = (int)(unsigned)double_to_bits(m);
-        bool sure = fabs(dd) > N_BOUNDARY_EPS && e < cx.Nd;
-        int n = ri + (dd < 0.0 ? 0 : 1);
-        if (STRATIFIED) {
-            const int fl = ri - (dd < 0.0 ? 1 : 0);
-            const double fr = dd < 0.0 ? dd + 1.0 : dd;
-            const double uf = cx.u_str[e < cx.Nd ? fl : 0];                // e >= 0 here
-            const double gap = uf - fr;
-            sure = sure && (gap > N_BOUNDARY_EPS || gap < -N_BOUNDARY_EPS);
-            n = fl + (gap > 0.0 ? 0 : 1);
-        }
-        unsure |= sure ? 0u : (1u << q);
-        nb[q] = n;
-    }
-    if (unsure) {                                                          // about one weight in 10^5: the exact tests
-        _Pragma("nounroll") for (int q = 0; q < OP_ITEMS; ++q) {
-            if (!(unsure & (1u << q))) continue;
-            double Eq = E[0];
-            FK_UNROLL for (int r = 1; r < OP_ITEMS; ++r) Eq = (q == r) ? E[r] : Eq;
-            const int n = n_boundary<STRATIFIED>((C0 + (excl + Eq)) * ulp, (int)cx.Np, cx.Nd, cx.halfNd, cx.u_sys, cx.u_str);
-            FK_UNROLL for (int r = 0; r < OP_ITEMS; ++r) nb[r] = (q == r) ? n : nb[r];
-        }
-    }
-}
-
-// slot boundaries from the cumulative sums a scan left in the tile (slots >= len take the carry-out: no slots)
-template <bool STRATIFIED>
-__device__ __forceinline__ void tile_boundaries(OpShared &sh, int len, double c_out, const ChunkCtx<STRATIFIED> &cx, int tid,
-                                                int (&nb)[OP_ITEMS])
-{
-    int *nslot = reinterpret_cast<int *>(&sh.tile[pad8(tid * OP_ITEMS)]);
-    _Pragma("nounroll") for (int q = 0; q < OP_ITEMS; ++q) {
-        const int j = tid * OP_ITEMS + q;
-        const double c = j < len ? sh.tile[pad8(j)] : c_out;
-        nslot[2 * q] = n_boundary_fast<STRATIFIED>(c, (int)cx.Np, cx.Nd, cx.halfNd, cx.u_sys, cx.u_str);
-    }
-    FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) nb[q] = nslot[2 * q];
-}
-
-// heads -> windows -> coalesced stores (the emission of resample_onepass_kernel); returns the chunk's last boundary
-__device__ __forceinline__ int emit_slots(OpShared &sh, int *win, const int (&nb)[OP_ITEMS], int u_lo, long base,
-                                          int32_t *of, int tid, bool win_ready)
-{
-    const int lane = tid & 63, wave = tid >> 6;
-    sh.nlast[tid] = nb[OP_ITEMS - 1];
-    __syncthreads();
-    int nprev = tid == 0 ? u_lo : sh.nlast[tid - 1];
-    const int u_hi = __builtin_amdgcn_readfirstlane(sh.nlast[OP_THREADS - 1]);
-    int head[OP_ITEMS];
-    FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-        head[q] = nb[q] > nprev ? nprev : -1;
-        nprev = nb[q] > nprev ? nb[q] : nprev;
-    }
-    const int mis = (int)(((uintptr_t)of >> 2) & 3);
-    int seed = -1;
-    for (int wb = u_lo - ((mis + u_lo) & 3); u_hi > u_lo && wb < u_hi; wb += OP_WIN) {        // uniform
-        if (!win_ready) {
-            __syncthreads();
-            init_window(win, tid);
-            __syncthreads();
-        }
-        win_ready = false;
-        int have = 0;
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-            const unsigned h = (unsigned)(head[q] - wb);
-            if (head[q] >= 0 && h < (unsigned)OP_WIN) {
-                win[h] = (int)base + tid * OP_ITEMS + q;
-                have = 1;
-            }
-        }
-        const int any_head = __syncthreads_or(have);
-        const int lim = u_hi - wb;
-        const int first = u_lo - wb;
-        int32_t *ow = of + wb;
-        const int s0 = 12 * tid;
-        int x[12];
-        if (any_head) {                                                    // uniform
-            FK_UNROLL for (int g = 0; g < 3; ++g) {
-                const i32x4 t = *reinterpret_cast<const i32x4 *>(&win[s0 + 4 * g]);
-                x[4 * g + 0] = t.x;
-                x[4 * g + 1] = t.y;
-                x[4 * g + 2] = t.z;
-                x[4 * g + 3] = t.w;
-            }
-            FK_UNROLL for (int e = 1; e < 12; ++e) x[e] = x[e] > x[e - 1] ? x[e] : x[e - 1];
-            const int wincl = wave_incl_max(x[11]);
-            if (lane == 63) sh.wmax[wave] = wincl;
-            __syncthreads();
-            const int up = __shfl_up(wincl, 1, 64);
-            int pre = (lane == 0 || up < seed) ? seed : up;
-            FK_UNROLL for (int wv = 0; wv < OP_THREADS / 64; ++wv) {
-                const int t = sh.wmax[wv];
-                if (wv < wave) pre = pre > t ? pre : t;
-                seed = seed > t ? seed : t;
-            }
-            FK_UNROLL for (int e = 0; e < 12; ++e) x[e] = x[e] > pre ? x[e] : pre;
-        } else {
-            FK_UNROLL for (int e = 0; e < 12; ++e) x[e] = seed;
-        }
-        if (s0 < lim) {
-            FK_UNROLL for (int g = 0; g < 3; ++g) {
-                const int s4 = s0 + 4 * g;
-                if (s4 >= first && s4 + 3 < lim) *reinterpret_cast<i32x4 *>(&ow[s4]) = i32x4{x[4 * g], x[4 * g + 1], x[4 * g + 2], x[4 * g + 3]};
-                else {
-                    FK_UNROLL for (int e = 0; e < 4; ++e)
-                        if (s4 + e >= first && s4 + e < lim) ow[s4 + e] = x[4 * g + e];
-                }
-            }
-        }
-    }
-    return u_hi;
-}
-
-__device__ __forceinline__ void load_chunk(double (&w8)[OP_ITEMS], const double *wf, long base, long Np, int tid)
-{
-    const int len = (int)((Np - base) < OP_TILE ? (Np - base) : OP_TILE);
-    const double *src = wf + base + tid * OP_ITEMS;
-    if (len == OP_TILE && (((uintptr_t)(wf + base)) & 15) == 0) {                              // uniform
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; q += 2) {
-            const f64x2 t = *reinterpret_cast<const f64x2 *>(src + q);
-            w8[q] = t.x;
-            w8[q + 1] = t.y;
-        }
-    } else if (len == OP_TILE) {
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) w8[q] = src[q];
-    } else {
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-            const int j = tid * OP_ITEMS + q;
-            const double t = wf[base + (j < len ? j : 0)];
-            w8[q] = j < len ? t : 0.0;
-        }
-    }
-}
-
+//
 // WAVES = workgroups per CU the registers are budgeted for.  Looped, the chunk body wants ~165 VGPRs: three per CU run
 // without a spill and are the faster ones while the chip is not full (125 x 8000: 39 vs 46 us); four per CU spill ~30
 // registers but hold 1024 filters at once -- one round instead of two for BASELINE configs[4]'s 1000 x 8000 (68 vs
@@ -1787,12 +1501,7 @@ resample_local_kernel(const OpArgs a)
     const int f = blockIdx.x;
     const double *wf = a.w + (long)f * Np;
     int32_t *of = a.idx + (long)f * Np;
-    ChunkCtx<STRATIFIED> cx;
-    cx.Np = Np;
-    cx.Nd = (double)Np;
-    cx.halfNd = 0.5 * cx.Nd;
-    cx.u_sys = STRATIFIED ? 0.0 : a.u[f];
-    cx.u_str = STRATIFIED ? a.u + (long)f * Np : nullptr;
+    const ChunkCtx<STRATIFIED> cx = chunk_ctx<STRATIFIED>(a, f);
     int *win = sh.win();
     double carry = 0.0;
     int u_lo = 0;
@@ -1819,20 +1528,9 @@ resample_local_kernel(const OpArgs a)
 #endif
 
         init_window(win, tid);
-        double s = 0.0, mn = 0.0;
-        FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-            s += w8[q];
-            mn = w8[q] < mn ? w8[q] : mn;
-        }
-        s = lane_bcast(wave_incl_sum(s), 63);
-        if (lane == 0) sh.seg.wtot[wave] = s;
-        const int any_neg = __syncthreads_or(mn < 0.0 ? 1 : 0);
+        const double S = chunk_sum(w8, sh.seg.wtot, lane, wave, bad);
         OP_CLOCK(1);                                                       // weights landed, chunk sum
-        const double S = (sh.seg.wtot[0] + sh.seg.wtot[1]) + (sh.seg.wtot[2] + sh.seg.wtot[3]);
-        if (any_neg || !(S < 0x1p1000)) {                                  // negative, NaN, Inf or absurdly large
-            bad = true;
-            break;
-        }
+        if (bad) break;                                                    // uniform
         int nb[OP_ITEMS];
         bool win_ready = true;
         double c_out = carry;
@@ -1845,24 +1543,7 @@ resample_local_kernel(const OpArgs a)
             int eu = 0;
             if (carry > OP_SANE_LO && carry < OP_SANE_HI) {                // uniform
                 eu = ulp_exp(carry);
-                bool tie = false;
-                double run = 0.0;
-                FK_UNROLL for (int q = 0; q < OP_ITEMS; ++q) {
-                    const double x = scale2(w8[q], -eu) + 0.5;
-                    const double i = floor(x);
-                    tie = tie || (i == x);
-                    run += i;
-                    E[q] = run;
-                }
-                const double winc = wave_incl_sum(run);
-                if (lane == 63) sh.wsum[wave] = winc;
-                const int any_tie = __syncthreads_or(tie ? 1 : 0);
-                excl = winc - run;
-                FK_UNROLL for (int wv = 0; wv < OP_THREADS / 64; ++wv) {
-                    if (wv < wave) excl += sh.wsum[wv];
-                    I += sh.wsum[wv];
-                }
-                fast = !any_tie && I < 0x1p53 && scale2(carry, -eu) + I < 0x1p53;
+                fast = chunk_increments(sh, w8, eu, lane, wave, E, excl, I) && scale2(carry, -eu) + I < 0x1p53;
             }
             OP_CLOCK(3);                                                   // increments
             if (fast) {                                                    // uniform
@@ -1894,7 +1575,7 @@ resample_local_kernel(const OpArgs a)
                 OP_COUNT(8, 1);
             }
         }
-        u_lo = emit_slots(sh, win, nb, u_lo, base, of, tid, win_ready);
+        u_lo = emit_slots(sh, win, nb, u_lo, base, of, tid, win_ready OP_NO_TIMERS);
         carry = c_out;
         __syncthreads();                                                   // the LDS slots are free for the next chunk
         OP_CLOCK(7);                                                       // emission
@@ -1909,8 +1590,7 @@ resample_local_kernel(const OpArgs a)
         }
         return;
     }
-    // ---- end of the vector: positions >= cumsum[-1] (the reference raises IndexError, resampling.py:109,145) --
-    for (long i = (long)u_lo + tid; i < Np; i += OP_THREADS) of[i] = (int32_t)(Np - 1);
+    fill_behind_cumsum(of, u_lo, Np, tid);
     if (tid == 0 && a.status) a.status[f] = u_lo < (int)Np ? ST_OVERRUN : 0;
 }
 

@@ -1,8 +1,8 @@
 // resample_onepass2.inc -- round 6's form of the one-pass kernel (included by resample_onepass.hip, inside namespace fk).
 //
-// Same protocol, same hand-off words, same exact arithmetic as resample_onepass_kernel (the chunks of one call may even be
-// resolved by a mix of the two code paths: op_chunk_slow below IS round 3's chunk) -- what changed is how many instructions and
-// barriers the COMMON chunk costs.  Round 5's phase clocks: 20 k clocks per chunk at five workgroups per CU, the SIMDs 0.56
+// Same protocol, same hand-off words, same exact arithmetic as resample_onepass_kernel (the chunks of one call are resolved by
+// a mix of the two code paths: op_chunk_slow and round 3's kernel both call op_resolve_chunk, ONE text in resample_onepass.hip)
+// -- what changed is how many instructions and barriers the COMMON chunk costs.  Round 5's phase clocks: 20 k clocks per chunk at five workgroups per CU, the SIMDs 0.56
 // busy issuing ~450 VALU instructions per wave and chunk, six workgroup barriers (two of them __syncthreads_or = three
 // s_barriers each).  The common chunk -- its binade guessed right, no tie, not the first and not the last of its vector -- now
 // takes:

@@ -1,5 +1,6 @@
 """Time fk_resample_systematic_f64 alone (no gather, no collective) on a few (filters, particles) shapes.
-    python tools/bench_resample.py [--shapes 125x8000000,1000x8000] [--iters 10]
+    python tools/bench_resample.py [--shapes 125x8000000,1000x8000] [--iters 10] [--stratified]
+--stratified times fk_resample_stratified_f64 instead (u of shape (filters, particles)): round 3's one-pass kernel in its production role.
 Prints one JSON line per shape; `tools/bench_c5.py` times the whole BASELINE configs[4] step instead."""
 import argparse
 import json
@@ -20,31 +21,33 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="125x8000000,8x8000000,1000x8000,125x8000")
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--stratified", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda")
+    resample = E.resample_stratified if a.stratified else E.resample_systematic
     for shape in a.shapes.split(","):
         Fn, Np = (int(v) for v in shape.split("x"))
         g = torch.Generator(device=dev)
         g.manual_seed(1)
         w = torch.rand((Fn, Np), generator=g, device=dev, dtype=torch.float64)
         w /= w.sum(dim=1, keepdim=True)
-        u = torch.rand(Fn, generator=g, device=dev, dtype=torch.float64)
+        u = torch.rand((Fn, Np) if a.stratified else Fn, generator=g, device=dev, dtype=torch.float64)
         idx = torch.empty((Fn, Np), dtype=torch.int32, device=dev)
         st = torch.zeros(Fn, dtype=torch.int32, device=dev)
         for _ in range(2):
-            E.resample_systematic(Fn, Np, w, u, idx, st)
+            resample(Fn, Np, w, u, idx, st)
         torch.cuda.synchronize()
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0.record()
         for _ in range(a.iters):
-            E.resample_systematic(Fn, Np, w, u, idx, st)
+            resample(Fn, Np, w, u, idx, st)
         t1.record()
         torch.cuda.synchronize()
         ms = t0.elapsed_time(t1) / a.iters
         # algorithmic bytes: w read once (8 B) + int32 index written (4 B) per particle
-        print(json.dumps({"filters": Fn, "particles": Np, "ms": round(ms, 4),
+        print(json.dumps({"scheme": "stratified" if a.stratified else "systematic", "filters": Fn, "particles": Np, "ms": round(ms, 4),
                           "particles_per_s": Fn * Np / ms * 1e3,
-                          "frac_hbm": 12.0 * Fn * Np / (ms * 1e-3) / 8e12}))
+                          "frac_hbm": (20.0 if a.stratified else 12.0) * Fn * Np / (ms * 1e-3) / 8e12}))   # (stratified: + u, 8 B)
 
 
 if __name__ == "__main__":
