@@ -327,7 +327,12 @@ FK_HD int kf_update(double (&x)[NX], double (&P)[NX * NX], const double (&z)[NZ]
         FK_UNROLL for (int i = 0; i < NX; ++i) K[i] = PHT[i] * si;
     } else {
         double d[NZ];
-        FK_UNROLL for (int i = 0; i < NZ * NZ; ++i) Lf[i] = S[i];
+        // S = H (P H') + R is symmetric only up to rounding and the factorisation reads one triangle: it gets (S + S') / 2,
+        // both triangles' rounding (the S that is returned stays as computed).  On P0 = 1e6 I, R = 1e-4 I at (16,8) with
+        // alpha_sq = 1.05 and update_first the means were 21 x the float64 reference's own error with one triangle, 7 x with
+        // both (docs/MEASUREMENTS.md, "KF options and variants precision").
+        FK_UNROLL for (int r = 0; r < NZ; ++r)
+            FK_UNROLL for (int c = 0; c < NZ; ++c) Lf[r * NZ + c] = 0.5 * (S[r * NZ + c] + S[c * NZ + r]);
         if (!ldlt2<NZ>(Lf, d, dinv)) st |= ST_NOT_PD;
         solve_rows_ldlt<NX, NZ>(Lf, dinv, K);
     }

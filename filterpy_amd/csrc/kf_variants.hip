@@ -198,6 +198,17 @@ corr_update_kernel(int n, int m, long N, const double *__restrict__ pH, const do
             FK_UNROLL for (int k = 1; k < NZ; ++k) acc = fma(K[i * NZ + k], W[k * NX + c], acc);
             P[i * NX + c] -= acc;
         }
+    // P - K W is symmetric only up to rounding, and nothing in this non-Joseph form damps the difference of the two triangles:
+    // through {predict; update_correlated} it grows until S = H P H' + ... is visibly unsymmetric, and the factorisation, which
+    // reads one triangle, solves with another matrix than the products used (up to 530 x the reference's own float64 error
+    // after 12 steps on P0 = 1e6 I, R = 1e-4 I; docs/MEASUREMENTS.md "KF options and variants precision").  Both triangles'
+    // rounding is kept, as in the packed-symmetric update (docs/KERNEL_NOTES.md).
+    FK_UNROLL for (int i = 0; i < NX; ++i)
+        FK_UNROLL for (int c = i + 1; c < NX; ++c) {
+            const double s = 0.5 * (P[i * NX + c] + P[c * NX + i]);
+            P[i * NX + c] = s;
+            P[c * NX + i] = s;
+        }
     store_rec<NX, 1, LAYOUT, false>(x, px, ln, n, 1);
     store_rec<NX, NX, LAYOUT, false>(P, pP, ln, n, n);
     if (py) store_rec<NZ, 1, LAYOUT, false>(y, py, ln, m, 1);
