@@ -392,16 +392,17 @@ def ukf_correct(n, m, N, layout, Pxz, zp, S, z, x, P, K=None, status=None):
     _abi.check(rc, "fk_ukf_correct_f64")
 
 
-def ukf_linear_supported(n, m, paired=False):
+def ukf_linear_supported(n, m, paired=False, simplex=False):
     """will fk_ukf_linear_batch_f64 take this size?  The LIBRARY answers (fk_ukf_linear_supported: csrc/ukf_kernels.hip, dim_x <= 9
-    one track per lane; 10..16: csrc/ukf_mlg.hip, several lanes per track, for weights equal within every +- pair), so the host
-    and the library cannot disagree about the library's A/B switches"""
-    return bool(_abi.lib().fk_ukf_linear_supported(int(n), int(m), _abi.FK_UKF_FLAG_PAIR_WEIGHTS if paired else 0, 0))
+    one track per lane; 10..16: csrc/ukf_mlg.hip, several lanes per track, for weights equal within every +- pair; simplex: the
+    n + 1 points of SimplexSigmaPoints, csrc/ukf_simplex.hip, dim_x <= 9), so the host and the library cannot disagree about the
+    library's A/B switches"""
+    return bool(_abi.lib().fk_ukf_linear_supported(int(n), int(m), _ukf_flags(None, None, n, bool(paired), simplex), 0))
 
 
-def ukf_linear_rts_supported(n, paired=False):
+def ukf_linear_rts_supported(n, paired=False, simplex=False):
     """will fk_ukf_linear_rts_f64 take this dim_x?  (asked of the library like ukf_linear_supported)"""
-    return bool(_abi.lib().fk_ukf_linear_supported(int(n), 1, _abi.FK_UKF_FLAG_PAIR_WEIGHTS if paired else 0, 1))
+    return bool(_abi.lib().fk_ukf_linear_supported(int(n), 1, _ukf_flags(None, None, n, bool(paired), simplex), 1))
 
 
 def pair_weights(Wm, Wc, n):
@@ -415,7 +416,17 @@ def pair_weights(Wm, Wc, n):
             and bool(np.array_equal(b[1:n + 1], b[n + 1:])))
 
 
-def _ukf_flags(Wm, Wc, n, paired):
+# `paired=SIMPLEX` of ukf_linear_batch / ukf_linear_rts: the point set is SimplexSigmaPoints (FK_UKF_FLAG_SIMPLEX).  One keyword names
+# the call's flag -- the signatures of these two wrappers are pinned operand by operand to the header's parameter names
+# (tests/test_host_logic.py), which leaves no room for a second flag keyword; the two `supported` questions take simplex=.
+SIMPLEX = "simplex"
+
+
+def _ukf_flags(Wm, Wc, n, paired, simplex=False):
+    """fk_ukf_desc.flags.  simplex (or paired is SIMPLEX): the point set is SimplexSigmaPoints -- n + 1 weights; the pair flag
+    means nothing there"""
+    if simplex or (isinstance(paired, str) and paired == SIMPLEX):
+        return _abi.FK_UKF_FLAG_SIMPLEX
     if paired is None:
         paired = pair_weights(Wm, Wc, n)
     return _abi.FK_UKF_FLAG_PAIR_WEIGHTS if paired else 0
@@ -423,7 +434,8 @@ def _ukf_flags(Wm, Wc, n, paired):
 
 def ukf_linear_batch(n, m, N, T, layout, scale, F, H, Q, R, Wm, Wc, z, x, P, *, mask=None,
                      means=None, covs=None, status=None, paired=None):
-    """fk_ukf_linear_batch_f64.  paired: None = look at the weights (pair_weights), True / False = the caller knows."""
+    """fk_ukf_linear_batch_f64.  paired: None = look at the weights (pair_weights), True / False = the caller knows;
+    SIMPLEX: FK_UKF_FLAG_SIMPLEX -- Wm / Wc hold n + 1 weights, scale is not read."""
     _keep = []
     d = fk_ukf_desc(n=n, m=m, N=N, T=T, layout=LAYOUTS[layout], flags=_ukf_flags(Wm, Wc, n, paired), scale=float(scale))
     rc = _abi.lib().fk_ukf_linear_batch_f64(d, _ptr(F), _ptr(H), _ptr(Q), _ptr(R), _ptr(Wm), _ptr(Wc),
@@ -433,7 +445,7 @@ def ukf_linear_batch(n, m, N, T, layout, scale, F, H, Q, R, Wm, Wc, z, x, P, *, 
 
 
 def ukf_linear_rts(n, N, T, layout, scale, F, Q, Wm, Wc, Xs, Ps, xs, Ps_out, K=None, status=None, paired=None):
-    """fk_ukf_linear_rts_f64: the UKF smoother's whole backward pass for a linear fx, one launch."""
+    """fk_ukf_linear_rts_f64: the UKF smoother's whole backward pass for a linear fx, one launch (paired: as in ukf_linear_batch)."""
     d = fk_ukf_desc(n=n, m=1, N=N, T=T, layout=LAYOUTS[layout], flags=_ukf_flags(Wm, Wc, n, paired), scale=float(scale))
     rc = _abi.lib().fk_ukf_linear_rts_f64(d, _ptr(F), _ptr(Q), _ptr(Wm), _ptr(Wc), _ptr(Xs), _ptr(Ps), _ptr(xs),
                                           _ptr(Ps_out), _ptr(K), _ptr(status), _stream())

@@ -21,6 +21,14 @@ FK_UKF_LAUNCHERS()
 FK_UKF_LAUNCHERS(_paired)
 #undef FK_UKF_LAUNCHERS
 
+// ukf_simplex.hip, one lane per track on the simplex point set (FK_UKF_FLAG_SIMPLEX): the same classes; tab: the point matrix's
+// (a_r, b_r) table, formed by the dispatcher (fk_ukf_simplex.hpp, simplex_table)
+struct SimplexTable;
+int ukf_simplex_fwd_launch_small(const UkfArgs &a, const SimplexTable &tab, int layout, hipStream_t s);
+int ukf_simplex_fwd_launch_big(const UkfArgs &a, const SimplexTable &tab, int layout, hipStream_t s);
+int ukf_simplex_rts_launch_small(const UkfRtsArgs &a, const SimplexTable &tab, const double *F, const double *Q, const double *Wm, const double *Wc, int layout, hipStream_t s);
+int ukf_simplex_rts_launch_big(const UkfRtsArgs &a, const SimplexTable &tab, const double *F, const double *Q, const double *Wm, const double *Wc, int layout, hipStream_t s);
+
 // ut_kernels.hip: the building blocks
 int launch_ut_points(int n, long N, int layout, double scale, const double *x, const double *P, double *sigmas, int32_t *status,
                      hipStream_t stream);

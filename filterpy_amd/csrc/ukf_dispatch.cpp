@@ -4,10 +4,12 @@
 //                                        ukf_mlg.hip); fk_ukf_linear_supported: which sizes they take (the host side asks first)
 // fk_ut_*_f64, fk_ukf_correct_f64     <- the building blocks of a filter with arbitrary fx / hx (ut_kernels.hip)
 // fk_ukf_rts_correct_f64              <- the gain / correction of rts_smoother (kf_variants.hip)
+// FK_UKF_FLAG_SIMPLEX: the same two calls on the n + 1 points of SimplexSigmaPoints (ukf_simplex.hip), a route of its own below.
 // These calls keep rules and words of their own (no check_desc): tests/test_host_refusals.py pins each branch and its place.
 #include "fk_dispatch.hpp"
 #include "fk_chunks.hpp"
 #include "fk_launchers.hpp"
+#include "fk_ukf_simplex.hpp"
 
 namespace fk {
 
@@ -68,6 +70,56 @@ static bool ukf_paired(const fk_ukf_desc *d)
     return !off && (d->flags & FK_UKF_FLAG_PAIR_WEIGHTS) != 0;
 }
 
+// FK_UKF_FLAG_SIMPLEX: the sizes the one-lane simplex kernels (ukf_simplex.hip) take -- the one-lane table of the other point
+// sets; nothing at dim_x 10..16, no switch
+static bool simplex_sizes(int n, int m, bool smoother)
+{
+    if (smoother) return n >= 1 && n <= 9;
+    return (n >= 1 && n <= 6 && m >= 1 && m <= 3) || (n >= 7 && n <= 9 && m >= 1 && m <= 4);
+}
+
+// The two fused calls with FK_UKF_FLAG_SIMPLEX: refusals in the order of the other route (size, bad argument, the 4 GiB guard,
+// nothing to do), then ONE launch.  Wm / Wc hold n + 1 weights, desc.scale is not read, FK_UKF_FLAG_PAIR_WEIGHTS is ignored.
+static int ukf_simplex_batch(const fk_ukf_desc *d, const double *F, const double *H, const double *Q, const double *R,
+                             const double *Wm, const double *Wc, const double *z, const uint8_t *mask, double *x, double *P,
+                             double *means, double *covs, int32_t *status, void *stream)
+{
+    if (!simplex_sizes(d->n, d->m, false))
+        return fail(FK_ERR_UNSUPPORTED, "fused linear UKF with FK_UKF_FLAG_SIMPLEX: dim_x 1..6 with dim_z 1..3, dim_x 7..9 with dim_z 1..4");
+    if (d->N < 0 || d->T < 0 || !F || !H || !Q || !R || !Wm || !Wc || !z || !x || !P)
+        return fail(FK_ERR_BAD_ARG, "fused linear UKF: bad argument");
+    if (int rc = check_record_block((double)d->N, (double)d->n * d->n, FK_4GIB - 32.0, "fused linear UKF: record block >= 4 GiB, split the batch"))
+        return rc;
+    if (d->N == 0 || d->T == 0) return FK_OK;
+    UkfArgs a{};
+    a.F = F; a.H = H; a.Q = Q; a.R = R; a.Wm = Wm; a.Wc = Wc; a.z = z; a.mask = mask;
+    a.x = x; a.P = P; a.means = means; a.covs = covs; a.status = status;
+    a.N = d->N; a.T = d->T; a.n = d->n; a.m = d->m; a.scale = 1.0;
+    a.i0 = 0; a.cnt = d->N; a.status_or = 0; a.soa_pairs = 0;
+    const SimplexTable tab = simplex_table(d->n);
+    return (a.n <= 6 && a.m <= 3) ? ukf_simplex_fwd_launch_small(a, tab, d->layout, (hipStream_t)stream)
+                                  : ukf_simplex_fwd_launch_big(a, tab, d->layout, (hipStream_t)stream);
+}
+
+static int ukf_simplex_rts(const fk_ukf_desc *d, const double *F, const double *Q, const double *Wm, const double *Wc,
+                           const double *Xs, const double *Ps, double *xs, double *Ps_out, double *K, int32_t *status, void *stream)
+{
+    if (!simplex_sizes(d->n, 1, true))
+        return fail(FK_ERR_UNSUPPORTED, "fused linear UKF smoother with FK_UKF_FLAG_SIMPLEX: dim_x 1..9");
+    if (d->N < 0 || d->T < 0 || !F || !Q || !Wm || !Wc || !Xs || !Ps || !xs || !Ps_out)
+        return fail(FK_ERR_BAD_ARG, "fused linear UKF smoother: bad argument");
+    if (int rc = check_record_block((double)d->N, (double)d->n * d->n, FK_4GIB, "fused linear UKF smoother: record block >= 4 GiB, split the batch"))
+        return rc;
+    if (d->N == 0 || d->T == 0) return FK_OK;
+    UkfRtsArgs a{};
+    a.Xs = Xs; a.Ps = Ps; a.xs = xs; a.ps = Ps_out; a.Ks = K; a.status = status;
+    a.N = d->N; a.T = d->T; a.n = d->n; a.scale = 1.0;
+    a.i0 = 0; a.cnt = d->N; a.cont = 0; a.status_or = 0;
+    const SimplexTable tab = simplex_table(d->n);
+    return a.n <= 6 ? ukf_simplex_rts_launch_small(a, tab, F, Q, Wm, Wc, d->layout, (hipStream_t)stream)
+                    : ukf_simplex_rts_launch_big(a, tab, F, Q, Wm, Wc, d->layout, (hipStream_t)stream);
+}
+
 }  // namespace fk
 
 using namespace fk;
@@ -76,6 +128,7 @@ extern "C" {
 
 int fk_ukf_linear_supported(int32_t n, int32_t m, int32_t flags, int32_t smoother)
 {
+    if (flags & FK_UKF_FLAG_SIMPLEX) return simplex_sizes(n, m, smoother != 0);
     const bool pairw = (flags & FK_UKF_FLAG_PAIR_WEIGHTS) != 0;
     if (smoother) {
         if (n >= 10 && n <= 16) return pairw && ukf_mlg_route().rts_min <= 10;
@@ -90,6 +143,7 @@ int fk_ukf_linear_batch_f64(const fk_ukf_desc *d, const double *F, const double 
                             double *means, double *covs, int32_t *status, void *stream)
 {
     if (!d) return fail(FK_ERR_BAD_ARG, "desc is NULL");
+    if (d->flags & FK_UKF_FLAG_SIMPLEX) return ukf_simplex_batch(d, F, H, Q, R, Wm, Wc, z, mask, x, P, means, covs, status, stream);
     // dim_x 10..16 (dim_z 1..8): four / eight lanes per track (ukf_mlg.hip), the pair-regrouped sums only
     const int fwd_min = ukf_mlg_route().fwd_min;
     const bool big = d->n >= 10 && d->n <= 16 && d->m >= 1 && d->m <= 8;
@@ -137,6 +191,7 @@ int fk_ukf_linear_rts_f64(const fk_ukf_desc *d, const double *F, const double *Q
 {
     const char *const guard = "fused linear UKF smoother: record block >= 4 GiB, split the batch";
     if (!d) return fail(FK_ERR_BAD_ARG, "desc is NULL");
+    if (d->flags & FK_UKF_FLAG_SIMPLEX) return ukf_simplex_rts(d, F, Q, Wm, Wc, Xs, Ps, xs, Ps_out, K, status, stream);
     // dim_x 10..16 -- and 7..9 for pair-weight callers (ukf_mlg_route) --: four / eight lanes per track (ukf_mlg.hip), pair-regrouped sums only
     const int rts_min = ukf_mlg_route().rts_min;
     const bool big = d->n >= 10 && d->n <= 16;

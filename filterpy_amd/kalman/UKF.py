@@ -35,6 +35,13 @@ fk_ukf_correct_f64 with zp = NULL takes y = residual_z(z, zp); state_add receive
                      U (N, n, n));
   device_callables   the same shapes on float64 CUDA tensors; nothing leaves HBM.
 sqrt_fn is stored as ``msqrt`` and, like in the reference (UKF.py:318-321), never used by the filter itself.
+
+Point sets: MerweScaledSigmaPoints, JulierSigmaPoints (2n+1 points) and SimplexSigmaPoints (n + 1 points, no scaling:
+sigma_points.py:386-534).  Everything behind the point generator runs on ``points.num_sigmas()``; the simplex set's own pieces
+are its generator on device records (_dev_simplex_sigmas: the factor kernel, then one batched product with the set's constant
+matrix) and the fused kernels' FK_UKF_FLAG_SIMPLEX.  Its `subtract` hook is called ONCE per filter like in the reference
+(sigma_points.py:512): subtract(x (n, 1), -U' I (n, n + 1)) -> (n, n + 1); vectorized / device_callables: once per call with a
+leading track axis, (N, n, 1) and (N, n, n + 1).
 """
 import sys
 from copy import deepcopy
@@ -113,6 +120,23 @@ class UnscentedKalmanFilter(_CallableHost):
         return (self.x_mean is not None or self.z_mean is not None or self.residual_x is not np.subtract
                 or self.residual_z is not np.subtract or self.state_add is not np.add
                 or getattr(pf, "_sqrt", None) is not None or getattr(pf, "_subtract", None) is not None)
+
+    @property
+    def _simplex(self):
+        """the point set is SimplexSigmaPoints: n + 1 points, no `scale` (the fused calls get FK_UKF_FLAG_SIMPLEX)"""
+        from .sigma_points import SimplexSigmaPoints
+        return isinstance(self.points_fn, SimplexSigmaPoints)
+
+    @property
+    def _scale(self):
+        """fk_ukf_desc.scale of the fused calls (not read with FK_UKF_FLAG_SIMPLEX)"""
+        return 1.0 if self._simplex else self.points_fn.scale
+
+    def _fused_kw(self):
+        """the keyword of E.ukf_linear_batch / _rts that names the point set's flag"""
+        if self._simplex:
+            return dict(paired=E.SIMPLEX)
+        return dict(paired=E.pair_weights(self.Wm, self.Wc, self._dim_x))
 
     @property
     def _linear(self):
@@ -215,6 +239,8 @@ class UnscentedKalmanFilter(_CallableHost):
         n, k, N, lay = self._dim_x, self._num_sigmas, self._N or 1, self._layout
         pf = self.points_fn
         sq, sb = getattr(pf, "_sqrt", None), getattr(pf, "_subtract", None)
+        if self._simplex:
+            return self._dev_simplex_sigmas(dx, dP, sig, st, sq, sb)
         if sq is None and sb is None:
             E.ut_sigma_points(n, N, lay, pf.scale, dx, dP, sig, st)
             return
@@ -227,6 +253,35 @@ class UnscentedKalmanFilter(_CallableHost):
         sub = np.subtract if sb is None else sb
         pts = torch.cat([x.unsqueeze(1), self._sub_from(sub, x, -U), self._sub_from(sub, x, U)], 1)
         sig.copy_(self._to_rec(pts, k, n).reshape(sig.shape))
+
+    def _dev_simplex_sigmas(self, dx, dP, sig, st, sq, sb):
+        """SimplexSigmaPoints.sigma_points on device records (sigma_points.py:499-513): U = sqrt(P) -- rows 1..n of the factor
+        kernel's points of a zero mean at scale 1, or the caller's sqrt_method --, then sigmas = x + I' U, one batched product
+        with the constant (n + 1) x n matrix I'; a custom subtract receives (x, -U' I) once per filter (once per call on the
+        bank in the vectorized / device conventions)."""
+        import torch
+        from .sigma_points import simplex_point_matrix
+        n, k, N, lay = self._dim_x, self._num_sigmas, self._N or 1, self._layout
+        x = self._vec_view(dx, n)
+        if sq is None:
+            pts = E.alloc_records((), N, (2 * n + 1) * n, lay)
+            E.ut_sigma_points(n, N, lay, 1.0, torch.zeros_like(dx), dP, pts, st)
+            U = self._rec_view(pts, 2 * n + 1, n)[:, 1:n + 1, :]
+        else:
+            U = self._sqrt(sq, self._rec_view(dP, n, n))
+        off = torch.matmul(E.dev(np.ascontiguousarray(simplex_point_matrix(n).T)).to(U.device), U)      # (N, n + 1, n): (U' I)'
+        if sb is None:
+            out = x.unsqueeze(1) + off
+        else:
+            xc, su = x.unsqueeze(2), -off.transpose(1, 2)                                              # (N, n, 1), (N, n, n + 1)
+            if self._mode == "torch":
+                out = sb(xc, su).transpose(1, 2)
+            elif self._mode == "vec":
+                out = self._tt(np.broadcast_to(sb(xc.cpu().numpy(), su.cpu().numpy()), su.shape), x).transpose(1, 2)
+            else:
+                xn, sn = xc.cpu().numpy(), su.cpu().numpy()
+                out = self._tt(np.array([np.asarray(sb(xn[i].copy(), sn[i].copy()), dtype=np.float64).T for i in range(N)]), x)
+        sig.copy_(self._to_rec(out.contiguous(), k, n).reshape(sig.shape))
 
     def _sub_from(self, fn, x, U):
         """subtract(x, U[k]) for every row k: x (N, n), U (N, n, n) -> (N, n, n)"""
@@ -537,7 +592,8 @@ class UnscentedKalmanFilter(_CallableHost):
         n, m = self._dim_x, self._dim_z
         fused = (self._linear and Rs is None and dts is None and saver is None and UT is None and not self._devcall
                  and not self._hooked and not isinstance(zs, torch.Tensor)
-                 and E.ukf_linear_supported(n, m, n >= 10 and E.pair_weights(self.Wm, self.Wc, n)))
+                 and (E.ukf_linear_supported(n, m, simplex=True) if self._simplex
+                      else E.ukf_linear_supported(n, m, n >= 10 and E.pair_weights(self.Wm, self.Wc, n))))
         with self._with_ut(UT):
             if self._resident and saver is None and not fused:
                 return self._dev_batch_filter(zs, Rs, dts, device_outputs)
@@ -567,11 +623,11 @@ class UnscentedKalmanFilter(_CallableHost):
             means, covs = E.alloc_records((T,), N, n, lay), E.alloc_records((T,), N, n * n, lay)
             st = status(N, dx)
             dm = None if mask.all() else torch.as_tensor(mask, device=dx.device)
-            E.ukf_linear_batch(n, m, N, T, lay, self.points_fn.scale, E.dev(self.fx), E.dev(self.hx),
+            E.ukf_linear_batch(n, m, N, T, lay, self._scale, E.dev(self.fx), E.dev(self.hx),
                                E.dev(np.broadcast_to(self.Q, (n, n)).copy()), E.dev(np.broadcast_to(self.R, (m, m)).copy()),
                                E.dev(np.asarray(self.Wm, dtype=np.float64)), E.dev(np.asarray(self.Wc, dtype=np.float64)),
                                E.to_records(zarr, lay, 1), dx, dP, mask=dm, means=means, covs=covs, status=st,
-                               paired=E.pair_weights(self.Wm, self.Wc, n))
+                               **self._fused_kw())
             E.raise_on_status(st, "UnscentedKalmanFilter.batch_filter")
             x_end = self._unb(E.from_records(dx, lay, 0, (n,)))
             P_end = self._unb(E.from_records(dP, lay, 0, (n, n)))
@@ -668,7 +724,8 @@ class UnscentedKalmanFilter(_CallableHost):
             raise ValueError('Xs and Ps must have the same length')
         fused = (not callable(self.fx) and dts is None and UT is None and not self._devcall and not self._hooked
                  and not isinstance(Xs, torch.Tensor)
-                 and E.ukf_linear_rts_supported(self._dim_x, self._dim_x >= 10 and E.pair_weights(self.Wm, self.Wc, self._dim_x)))
+                 and (E.ukf_linear_rts_supported(self._dim_x, simplex=True) if self._simplex
+                      else E.ukf_linear_rts_supported(self._dim_x, self._dim_x >= 10 and E.pair_weights(self.Wm, self.Wc, self._dim_x))))
         with self._with_ut(UT):
             if (self._resident or isinstance(Xs, torch.Tensor)) and not fused:
                 return self._dev_rts_smoother(Xs, Ps, dts, device_outputs)
@@ -681,10 +738,10 @@ class UnscentedKalmanFilter(_CallableHost):
             dP = E.to_records(np.asarray(Ps, dtype=np.float64).reshape(T, N, n, n), lay, 1)
             oxs, ops, oK = E.alloc_records((T,), N, n, lay), E.alloc_records((T,), N, n * n, lay), E.alloc_records((T,), N, n * n, lay)
             st = status(N, dX)
-            E.ukf_linear_rts(n, N, T, lay, self.points_fn.scale, E.dev(np.asarray(self.fx, dtype=np.float64)),
+            E.ukf_linear_rts(n, N, T, lay, self._scale, E.dev(np.asarray(self.fx, dtype=np.float64)),
                              E.dev(np.broadcast_to(np.asarray(self.Q, dtype=np.float64), (n, n)).copy()),
                              E.dev(np.asarray(self.Wm, dtype=np.float64)), E.dev(np.asarray(self.Wc, dtype=np.float64)),
-                             dX, dP, oxs, ops, oK, st, paired=E.pair_weights(self.Wm, self.Wc, n))
+                             dX, dP, oxs, ops, oK, st, **self._fused_kw())
             E.raise_on_status(st, "UnscentedKalmanFilter.rts_smoother")
             xs, ps, Ks = E.from_records(oxs, lay, 1, (n,)), E.from_records(ops, lay, 1, (n, n)), E.from_records(oK, lay, 1, (n, n))
             if self._N is None:

@@ -6,7 +6,7 @@ from .fixed_lag_smoother import FixedLagSmoother, FixedLagSmootherBank  # noqa: 
 from .square_root import SquareRootKalmanFilter, SquareRootKalmanFilterBank  # noqa: F401
 from .information_filter import InformationFilter, InformationFilterBank  # noqa: F401
 from .ensemble_kalman_filter import EnsembleKalmanFilter, EnsembleKalmanFilterBank  # noqa: F401
-from .sigma_points import MerweScaledSigmaPoints, JulierSigmaPoints  # noqa: F401
+from .sigma_points import MerweScaledSigmaPoints, JulierSigmaPoints, SimplexSigmaPoints  # noqa: F401
 from .unscented_transform import unscented_transform  # noqa: F401
 from .UKF import UnscentedKalmanFilter  # noqa: F401
 from .CubatureKalmanFilter import CubatureKalmanFilter, spherical_radial_sigmas, ckf_transform  # noqa: F401

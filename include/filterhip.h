@@ -491,7 +491,7 @@ int fk_ukf_correct_f64(int32_t n, int32_t m, int64_t N, int32_t layout,
 
 /* fk_ukf_desc.flags */
 enum {
-    FK_UKF_FLAG_PAIR_WEIGHTS = 1   /* the caller asserts Wm[1+k] == Wm[1+n+k] and Wc[1+k] == Wc[1+n+k] for k = 0..n-1 (true of
+    FK_UKF_FLAG_PAIR_WEIGHTS = 1,  /* the caller asserts Wm[1+k] == Wm[1+n+k] and Wc[1+k] == Wc[1+n+k] for k = 0..n-1 (true of
                                       MerweScaledSigmaPoints and JulierSigmaPoints, sigma_points.py:180-192, :358-372): the sums
                                       of unscented_transform.py:104-126 and UKF.py:483-497 are then formed over the n +- PAIRS of
                                       sigma points (a re-association of the reference's index-order sums: every factor, image and
@@ -499,6 +499,17 @@ enum {
                                       Without the flag -- and for every other weight set -- the sums run in the reference's index
                                       order.  Environment FK_UKF_PAIRED=0 ignores the flag (A/B).  A violated assertion is
                                       reported as FK_STATUS_BAD_WEIGHTS on every track. */
+    /* (bit value 2 is not a flag: these calls ignore it) */
+    FK_UKF_FLAG_SIMPLEX = 4        /* the point set is SimplexSigmaPoints (filterpy/kalman/sigma_points.py:386-534): n + 1 points
+                                      sigmas = x + U' I with U = cholesky(P) -- no scaling: desc.scale is NOT READ -- and the
+                                      constant n x (n + 1) matrix I = sqrt(n) Istar of :501-509, which the library forms itself
+                                      from n.  Wm and Wc then have n + 1 entries and are used as given, point by point in index
+                                      order (:516-522 makes them all 1 / (n + 1); nothing relies on that, nor on their sum).
+                                      FK_UKF_FLAG_PAIR_WEIGHTS is ignored next to this flag.  Sizes: the filter at dim_x 1..6 with
+                                      dim_z 1..3 and dim_x 7..9 with dim_z 1..4, the smoother at dim_x 1..9, one track per lane
+                                      (ukf_simplex.hip); any other size -- dim_x 10..16 included -- answers FK_ERR_UNSUPPORTED
+                                      and fk_ukf_linear_supported says so beforehand: the building blocks take a point count
+                                      and serve every size. */
 };
 
 typedef struct fk_ukf_desc {
@@ -518,7 +529,8 @@ typedef struct fk_ukf_desc {
  *   means [T][N][n], covs [T][N][n*n] posterior per step (NULL = not stored).
  * Sizes: dim_x 1..6 with dim_z 1..3, dim_x 7..9 with dim_z 1..4 (one track per lane, ukf_kernels.hip); dim_x 10..16 with
  * dim_z 1..8 on four / eight lanes per track (ukf_mlg.hip) for FK_UKF_FLAG_PAIR_WEIGHTS callers; FK_ERR_UNSUPPORTED
- * otherwise (the building blocks serve every size) -- fk_ukf_linear_supported answers without a launch. */
+ * otherwise (the building blocks serve every size) -- fk_ukf_linear_supported answers without a launch.
+ * FK_UKF_FLAG_SIMPLEX: Wm, Wc [n+1], scale not read, the one-lane sizes only (ukf_simplex.hip; see the flag). */
 int fk_ukf_linear_batch_f64(const fk_ukf_desc *desc,
                             const double *F, const double *H, const double *Q, const double *R,
                             const double *Wm, const double *Wc,
@@ -536,7 +548,8 @@ int fk_ukf_linear_batch_f64(const fk_ukf_desc *desc,
  *   [T][N][n*n] or NULL (K of the last step is zero, like the reference's); status [N] or NULL.
  * Asynchronous on `stream` and ordered like one kernel on it; at dim_x >= 5 a call whose last round of waves would be
  * mostly idle fans out over up to three helper streams like fk_kf_batch_filter_f64 (bit-identical; FK_UKF_RTS_CHUNKS=1,1
- * turns it off; INTEGRATION.md, "Streams"). */
+ * turns it off; INTEGRATION.md, "Streams").
+ * FK_UKF_FLAG_SIMPLEX: Wm, Wc [n+1], scale not read, dim_x 1..9, always one launch on `stream` (ukf_simplex.hip; see the flag). */
 int fk_ukf_linear_rts_f64(const fk_ukf_desc *desc, const double *F, const double *Q, const double *Wm, const double *Wc,
                           const double *Xs, const double *Ps, double *xs, double *Ps_out, double *K, int32_t *status,
                           void *stream);

@@ -7,6 +7,7 @@ oracle on one track.  The launchers read their A/B switch (FK_UKF_PADDED) once p
 A/B comparison is two invocations of this script in one lease; the line carries the switches it ran under.
 
     python tools/bench_ukf.py --dims 6x3,4x2,8x4 --N 100000 --T 100
+    python tools/bench_ukf.py --points simplex --dims 6x3      # the simplex kernels next to the Merwe paired ones, same process
 """
 import argparse
 import json
@@ -102,6 +103,72 @@ def run(n, m, N, T, layout, dense):
                           parity_max_rel=par, switches=sw)), flush=True)
 
 
+def run_simplex(n, m, N, T, layout, dense, reps=10):
+    """--points simplex: fk_ukf_linear_batch_f64 / _rts_f64 with FK_UKF_FLAG_SIMPLEX (csrc/ukf_simplex.hip, n + 1 points) and, in
+    the same process on the same inputs, the Merwe pair-weight kernels: `reps` event-timed launches each after warm-up, the
+    median, and the ratio simplex / Merwe.  Parity of the simplex outputs on the bank's last track against tests/simplex_port.py."""
+    import torch
+    from filterpy_amd import _engine as E
+    from oracle import ukf_oracle
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import simplex_port as sp
+    alpha, beta, kappa = .1, 2., 3. - n
+    lam = alpha ** 2 * (n + kappa) - n
+    Wm, Wc = ukf_oracle.merwe_weights(n, alpha, beta, kappa)
+    Ws = sp.weights(n)
+    F, H, Q, R = model(n, m)
+    if dense:
+        r = np.random.default_rng(1)
+        F = F + 0.01 * r.standard_normal((n, n))
+        H = H + 0.01 * r.standard_normal((m, n))
+    dev = torch.device("cuda")
+    g = torch.Generator(device=dev)
+    g.manual_seed(4)
+    z = torch.randn((T, N, m) if layout == "aos" else (T, m, N), generator=g, device=dev, dtype=torch.float64)
+    x0 = torch.randn((N, n) if layout == "aos" else (n, N), generator=g, device=dev, dtype=torch.float64)
+    P0 = (10.0 * torch.eye(n, dtype=torch.float64, device=dev)).reshape(1, n * n).repeat(N, 1)
+    P0 = P0.contiguous() if layout == "aos" else P0.T.contiguous()
+    x, P = x0.clone(), P0.clone()
+    means, covs = E.alloc_records((T,), N, n, layout), E.alloc_records((T,), N, n * n, layout)
+    xs, Ps, Ks = E.alloc_records((T,), N, n, layout), E.alloc_records((T,), N, n * n, layout), E.alloc_records((T,), N, n * n, layout)
+    st = torch.zeros(N, dtype=torch.int32, device=dev)
+    dF, dH, dQ, dR, dWm, dWc, dWs = (E.dev(M) for M in (F, H, Q, R, Wm, Wc, Ws))
+
+    def fwd(simplex):
+        x.copy_(x0)
+        P.copy_(P0)
+        if simplex:
+            E.ukf_linear_batch(n, m, N, T, layout, 1.0, dF, dH, dQ, dR, dWs, dWs, z, x, P, means=means, covs=covs, status=st, paired=E.SIMPLEX)
+        else:
+            E.ukf_linear_batch(n, m, N, T, layout, lam + n, dF, dH, dQ, dR, dWm, dWc, z, x, P, means=means, covs=covs, status=st, paired=True)
+
+    def rts(simplex):
+        if simplex:
+            E.ukf_linear_rts(n, N, T, layout, 1.0, dF, dQ, dWs, dWs, means, covs, xs, Ps, K=Ks, status=st, paired=E.SIMPLEX)
+        else:
+            E.ukf_linear_rts(n, N, T, layout, lam + n, dF, dQ, dWm, dWc, means, covs, xs, Ps, K=Ks, status=st, paired=True)
+    trk = N - 1
+    zs_h = (z[:, trk] if layout == "aos" else z[:, :, trk]).cpu().numpy()
+    x0h = (x0[trk] if layout == "aos" else x0[:, trk]).cpu().numpy()
+    ms = {}
+    for simplex in (False, True):              # the smoother of each point set runs on that set's own filter output
+        ms["fwd", simplex] = timeit(lambda: fwd(simplex), reps=reps)
+        assert not st.any()
+        if simplex:
+            mu_ref, cov_ref = sp.batch_filter(x0h, 10 * np.eye(n), list(zs_h), F, H, Q, R)
+            par_f = max(sp.rel(E.from_records(means, layout, 1, (n,))[:, trk], mu_ref),
+                        sp.rel(E.from_records(covs, layout, 1, (n, n))[:, trk], cov_ref))
+        ms["rts", simplex] = timeit(lambda: rts(simplex), reps=reps)
+        assert not st.any()
+        if simplex:
+            ref = sp.rts_smoother(mu_ref, cov_ref, F, Q)
+            par_r = max(sp.rel(E.from_records(a, layout, 1, s)[:, trk], w) for a, s, w in zip((xs, Ps, Ks), ((n,), (n, n), (n, n)), ref))
+    for kind, par, what in (("fwd", par_f, f"fused simplex UKF ({n},{m}) {layout}"), ("rts", par_r, f"fused simplex UKF smoother n={n} {layout}")):
+        print(json.dumps(dict(kernel=what, N=N, T=T, dense_model=dense, launches=reps, ms=ms[kind, True], merwe_paired_ms=ms[kind, False],
+                              ratio_simplex_over_merwe=ms[kind, True] / ms[kind, False],
+                              track_steps_per_s=N * T / (ms[kind, True] * 1e-3), parity_max_rel=par)), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--dims", default="6x3")
@@ -110,9 +177,14 @@ if __name__ == "__main__":
     ap.add_argument("--T", type=int, default=100)
     ap.add_argument("--dense", action="store_true", help="dense F and H instead of the constant-velocity pattern")
     ap.add_argument("--no-outputs", action="store_true", help="forward kernel only, per-step histories not stored (how much of the step is the store path?)")
+    ap.add_argument("--points", default="merwe", choices=["merwe", "simplex"],
+                    help="simplex: the n + 1-point kernels next to the Merwe pair-weight kernels in one process (10 launches each)")
     a = ap.parse_args()
     NO_OUTPUTS = a.no_outputs
     for d in a.dims.split(","):
         n, m = (int(v) for v in d.split("x"))
         for lay in a.layouts.split(","):
-            run(n, m, a.N, a.T, lay, a.dense)
+            if a.points == "simplex":
+                run_simplex(n, m, a.N, a.T, lay, a.dense)
+            else:
+                run(n, m, a.N, a.T, lay, a.dense)
