@@ -21,6 +21,7 @@ FK_MODEL_SHARED, FK_MODEL_PER_TRACK, FK_MODEL_PER_TRACK_STEP, FK_MODEL_PER_STEP 
 FK_STATUS_NOT_PD, FK_STATUS_NONFINITE, FK_STATUS_OVERRUN, FK_STATUS_INTERNAL, FK_STATUS_BAD_WEIGHTS = 1, 2, 4, 8, 16
 FK_UKF_FLAG_PAIR_WEIGHTS = 1
 FK_UKF_FLAG_SIMPLEX = 4          # (2 is not a flag)
+FK_POLY_FORM_A, FK_POLY_FORM_B, FK_POLY_FORM_C = 0, 1, 2         # fk_poly_run: multiply / divide / Zarchan (csrc/fk_poly.hpp)
 
 c_i32, c_i64, c_f64, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t
 
@@ -99,6 +100,7 @@ SIGNATURES = {
     "fk_ukf_linear_rts_f64": (ctypes.c_int, [ctypes.POINTER(fk_ukf_desc)] + [c_vp] * 11),
     "fk_ukf_linear_supported": (ctypes.c_int, [ctypes.c_int32] * 4),
     "fk_kf_steadystate_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 12),
+    "fk_poly_run": (ctypes.c_int, [c_i32, c_i32, c_i64, c_i64, c_i32] + [c_f64] * 6 + [c_vp] * 7),
     "fk_kf_update_correlated_f64": (ctypes.c_int, [ctypes.POINTER(fk_kf_desc)] + [c_vp] * 13),
     "fk_ukf_rts_correct_f64": (ctypes.c_int, [c_i32, c_i64, c_i32] + [c_vp] * 10),
     "fk_imm_batch_f64": (ctypes.c_int, [ctypes.POINTER(fk_imm_desc)] + [c_vp] * 17),

@@ -461,6 +461,15 @@ def kf_steadystate(desc_kw, F, H, K, z, x, *, B=None, u=None, mask=None, means=N
     _abi.check(rc, "fk_kf_steadystate_f64")
 
 
+def poly_run(order, form, N, T, layout, dt, T2, c, g0, g1, g2, z, x, *, gains=None, xs=None, pred=None, y=None):
+    """fk_poly_run: T steps of a fixed-gain polynomial filter (g-h / g-h-k, fading memory, least squares) for N tracks.
+    form: _abi.FK_POLY_FORM_A / _B / _C; gains: None (g0..g2 at every step) or a device table [T][order + 1]."""
+    rc = _abi.lib().fk_poly_run(int(order), int(form), int(N), int(T), LAYOUTS[layout], float(dt), float(T2), float(c),
+                                float(g0), float(g1), float(g2), _ptr(gains), _ptr(z), _ptr(x), _ptr(xs), _ptr(pred), _ptr(y),
+                                _stream())
+    _abi.check(rc, "fk_poly_run")
+
+
 def kf_update_correlated(desc_kw, H, R, M, z, x, P, *, mask=None, y=None, K=None, S=None, SI=None, status=None):
     _keep = []
     d = fk_kf_desc(**desc_kw)

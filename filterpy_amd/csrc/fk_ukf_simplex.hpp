@@ -38,7 +38,8 @@ struct SimplexTable {
 
 // sigma_points.py:501-509 in its operation order.  Row 1 is [-1/sqrt(2 lambda), +1/sqrt(2 lambda)] -- the general rule
 // negated --, row d >= 2 is 1./sqrt(lambda d (d+1)) in the columns 0..d-1 and -d/sqrt(lambda d (d+1)) in column d; the whole
-// matrix is then multiplied by sqrt(n).  Host only: the device has no correctly rounded sqrt / division to offer.
+// matrix is then multiplied by sqrt(n).  Host only: the table is the same for every track, and the device's
+// sqrt has not been held to the host's bits (its fp64 `/` has: docs/KERNEL_NOTES.md, "polynomial filters").
 inline SimplexTable simplex_table(int n)
 {
     SimplexTable t;

@@ -580,6 +580,39 @@ int fk_kf_steadystate_f64(const fk_kf_desc *desc,
                           double *x, double *means, double *means_p, double *y_out,
                           void *stream);
 
+/* The fixed-gain polynomial filters for N tracks, T steps in one launch: GHFilter / GHKFilter / GHFilterOrder
+ * (filterpy/gh/gh_filter.py), FadingMemoryFilter (filterpy/memory/fading_memory.py) and LeastSquaresFilter
+ * (filterpy/leastsq/least_squares.py).  All of them are one recurrence on a state (x, dx, ddx) of order + 1 components,
+ * order 0..2; the results are the reference's BITS, so the association of every sum is part of the contract
+ * (csrc/fk_poly.hpp).  Three operation orders exist in the reference:
+ *   FK_POLY_FORM_A  multiply: GHFilter.batch_filter (gh_filter.py:433-442), GHKFilter.batch_filter (:729-738), GHFilterOrder
+ *     order 0 (:145-146), FadingMemoryFilter (fading_memory.py:164-194), LeastSquaresFilter order 0 (least_squares.py:131-133)
+ *       xp = (x + dx*dt) + (0.5*ddx)*T2 ; dxp = dx + ddx*dt ; r = z - xp
+ *       x' = xp + g0*r ; dx' = dxp + g1*r ; ddx' = ddx + g2*r                     orders 0, 1, 2; reads dt, T2, g0..g2
+ *   FK_POLY_FORM_B  divide: GHFilter.update (:368-375), GHKFilter.update (:666-678), GHFilterOrder orders 1, 2 (:153-181)
+ *       xp, dxp, r as in A ; x' = xp + g0*r ; dx' = dxp + (g1*r)/dt ; ddx' = ddx + (g2*r)/T2
+ *                                                                                 orders 1, 2; g0 = g, g1 = h, g2 = 2*k
+ *   FK_POLY_FORM_C  Zarchan: LeastSquaresFilter orders 1, 2 (:136-154)
+ *       y = ((z - x0) - dt*x1) - c*x2 ; x0' = x0 + (((g0*y) + x1*dt) + c*x2) ; x1' = x1 + ((g1*y) + x2*dt) ; x2' = x2 + g2*y
+ *       every right-hand side reads the old state                                 orders 1, 2; reads dt, c = 0.5*dt**2
+ *   Terms of a component the order does not have are absent.  T2 = dt**2, c and the gains are the caller's scalars, computed
+ *   with the reference's own expressions; any other (order, form) is FK_ERR_UNSUPPORTED.
+ *   gains: NULL (every step uses g0..g2) or a device table [T][order+1] shared by all tracks (LeastSquaresFilter: the gains
+ *   depend on the step count alone).  Gains per track are not served.
+ *   layout, with c = order + 1: FK_LAYOUT_SOA x [c][N], xs [T][c][N]; FK_LAYOUT_AOS x [N][c], xs [T][N][c].
+ *   z [T][N]; x in/out; optional outputs (NULL: not written): xs the state after every step, pred [T][N] the predicted
+ *   position xp (form C: (x0 + dt*x1) + c*x2), y_out [T][N] the residual.  T = 0 or N = 0: FK_OK, nothing done. */
+#define FK_POLY_FORM_A 0
+#define FK_POLY_FORM_B 1
+#define FK_POLY_FORM_C 2
+int fk_poly_run(int32_t order, int32_t form, int64_t N, int64_t T, int32_t layout,
+                double dt, double T2, double c, double g0, double g1, double g2,
+                const double *gains,
+                const double *z,
+                double *x,
+                double *xs, double *pred, double *y_out,
+                void *stream);
+
 /* KalmanFilter.update_correlated (kalman_filter.py:670-752): process and measurement noise correlated
  * through M (dim_x x dim_z):  y = z - H x ; S = H P H' + H M + M' H' + R ; K = (P H' + M) S^-1 ;
  * x += K y ; P -= K (H P + M').   One update of N tracks.
